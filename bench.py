@@ -3,8 +3,15 @@
 
     python bench.py --gpus N --steps K --warmup W                 # headline (N > 1: one
                                                                   #   child rank per GPU)
+    python bench.py --gpus N --steps K --warmup W --full          # + AUC, per-phase figures,
+                                                                  #   end-to-end fit
+    python bench.py ... --dump-outputs DIR                        # + the timed path's outputs (.npy)
     torchrun --nproc-per-node N bench.py --gpus N ...             # driver, N > 1
     python bench.py --model xgboost-airlines | dl-mlp ...         # other BASELINE configs
+
+A plain run sets up, warms up, times the K steps and prints one JSON result
+line (``value``, ``ms_per_step`` = milliseconds per timed step, ...);
+everything measured or checked besides that runs only with ``--full``.
 
 Headline (default, ``--model gbm-higgs``): GBM binomial training throughput
 on HIGGS-shape 11M x 28 synthetic data.  One *step* is one full boosting
@@ -17,11 +24,11 @@ default for the headline: the metric is "HIGGS-shape 11M x 28 at 1/2/4/8
 MI355X", so the same 11M rows (same seed) are split over the N ranks and
 N ranks grow the 1-rank trees; ``--scaling weak`` gives every rank its own
 11M-row shard instead (global rows = N x 11M).  Each step is replayed as a
-HIP graph when eligible (``--tree-graph``); after the timed steps a few
-instrumented steps report the host-enqueue, per-phase and collective time
-per tree.  Training AUC of the final model (all ranks) is reported;
-``--oracle-rows R`` adds a scikit-learn HistGradientBoosting fit on R rows
-for AUC parity.
+HIP graph when eligible (``--tree-graph``).  With ``--full``, after the
+timed steps, the training AUC of the final model (all ranks) is reported, a
+few instrumented steps report the host-enqueue, per-phase and collective time
+per tree, and a whole 50-tree fit is timed end to end; ``--oracle-rows R``
+adds a scikit-learn HistGradientBoosting fit on R rows for AUC parity.
 
 ``xgboost-airlines``: XGBoost-hist (second-order gain, depth 6, eta 0.3) on
 Airlines-shape 31-column data, 150M rows over 8 GPUs = 18.75M rows per GPU
@@ -65,6 +72,45 @@ def _timed(step, args, comm, torch, dev, finish=None):
     comm.barrier()
     _sync(torch, dev)
     return comm.max_scalar(time.perf_counter() - t0)
+
+
+DUMP_BUDGET_BYTES = 60 << 20   # --dump-outputs: all files of all ranks together stay under 64 MB
+
+
+def _dump_outputs(args, rank, np, arrays):
+    """``--dump-outputs DIR``: save what the timed path computed as
+    ``DIR/<name>.npy`` (rank r > 0: ``<name>.rank<r>.npy``), float32 / float64.
+    The rank's share of the size budget is dealt out smallest array first; an
+    array over what is left for it is cut down to a fixed sample of its
+    flattened elements (sorted indices drawn with ``--seed``), so two runs with
+    the same arguments write the same positions."""
+    os.makedirs(args.dump_outputs, exist_ok=True)
+    left = DUMP_BUDGET_BYTES // max(args.gpus, 1)
+    arrays = {name: np.ascontiguousarray(a, dtype=np.float64 if a.dtype == np.float64 else np.float32)
+              for name, a in arrays.items()}
+    for i, (name, a) in enumerate(sorted(arrays.items(), key=lambda kv: kv[1].nbytes)):
+        share = left // (len(arrays) - i)
+        if a.nbytes > share:
+            idx = np.sort(np.random.default_rng(args.seed).choice(a.size, size=share // a.itemsize, replace=False))
+            a = a.reshape(-1)[idx]
+        left -= a.nbytes
+        np.save(os.path.join(args.dump_outputs, f"{name}.npy" if rank == 0 else f"{name}.rank{rank}.npy"), a)
+
+
+def _tree_table(np, trees):
+    """[ntrees][nodes][6] float64 (feat, bin, na_left, value, left, thr) of the
+    nodes reachable from each root; everything else is 0 (device tree heaps
+    leave unreachable slots, and a leaf's child link, unwritten)."""
+    out = np.zeros((trees.shape[0], trees.shape[1], 6), np.float64)
+    for t, tr in enumerate(trees):
+        stack = [0]
+        while stack:
+            i = stack.pop()
+            out[t, i, :4] = (tr[i]["feat"], tr[i]["bin"], tr[i]["na_left"], tr[i]["value"])
+            if tr[i]["feat"] >= 0:
+                out[t, i, 4:] = (tr[i]["left"], tr[i]["thr"])
+                stack += [int(tr[i]["left"]), int(tr[i]["left"]) + 1]
+    return out
 
 
 def _trees(args, comm, torch, np, model):
@@ -164,18 +210,28 @@ def _trees(args, comm, torch, np, model):
         margin = torch.from_numpy(ens._cpu_margin[0])
         coll, graph_used, graph_group = comm.collective_stats(), False, 0
     total_rows = int(comm.all_reduce_numpy(np.array([float(n_local)]))[0])
+    if args.dump_outputs:
+        # what the timed steps left behind, before anything below trains further
+        if gb is not None:
+            from h2omx.models.tree.boost import _GpuView
+
+            trees = _GpuView(gb).trees(0, gb.t)
+        else:
+            trees = ens.trees
+        _dump_outputs(args, rank, np, {"margin": margin.detach().cpu().numpy(), "trees": _tree_table(np, trees)})
     if args.dump_trees:
         trees = gb.finish().trees if gb is not None else ens.trees
         if rank == 0:
             np.save(args.dump_trees, trees)
     auc = None
-    if not args.no_auc:
+    if args.full and not args.no_auc:
         auc = auc_from_scores(margin, y, comm=comm)
     per_tree = None
     if gb is not None and args.instrument_steps > 0:
         per_tree = _instrument(gb, args, tcomm, torch, dev)
     fit = None
-    fit_trees = args.fit_trees if args.fit_trees >= 0 else (50 if dev.type == "cuda" and tcomm is comm else 0)
+    fit_trees = args.fit_trees if args.fit_trees >= 0 else (
+        50 if args.full and dev.type == "cuda" and tcomm is comm else 0)
     if fit_trees > 0:
         gb = None   # release the timed booster's buffers before the end-to-end fit
         fit = _fit_end_to_end(X, y, fit_trees, tp, args, comm, torch, dev, total_rows)
@@ -422,12 +478,16 @@ def _mlp(args, comm, torch, np):
     elapsed = _timed(step, args, comm, torch, dev, finish=trainer.flush if trainer is not None else None)
     if trainer is not None:
         trainer.sync()
-    with torch.no_grad():
-        xs, ys_ = X[:200_000], y[:200_000]
-        from h2omx.metrics.core import auc_from_scores
+    if args.dump_outputs:
+        _dump_outputs(args, rank, np, {"weights": net.flat.detach().cpu().numpy()})
+    auc = None
+    if args.full:
+        with torch.no_grad():
+            xs, ys_ = X[:200_000], y[:200_000]
+            from h2omx.metrics.core import auc_from_scores
 
-        Z = _forward(net, xs, 1, False, 0.0, [0.0] * 8, None)[0][-1]
-        auc = auc_from_scores(torch.softmax(Z, 1)[:, 1], ys_, comm=comm)
+            Z = _forward(net, xs, 1, False, 0.0, [0.0] * 8, None)[0][-1]
+            auc = auc_from_scores(torch.softmax(Z, 1)[:, 1], ys_, comm=comm)
     flops_row = 6 * sum(a * b for a, b in zip([200, 512, 512, 512, 512], [512, 512, 512, 512, 2]))
     return {
         "metric": "H2O DeepLearning MLP 4×512 on 50M×200 synthetic (6.25M rows per MI355X): train samples/sec",
@@ -478,10 +538,18 @@ def main(argv=None) -> int:
     ap.add_argument("--scaling", choices=["weak", "strong"], default=None,
                     help="gbm-higgs default strong (11M rows in total, split over the ranks: the headline metric's "
                          "config at every N); xgboost-airlines / dl-mlp default weak (their configs are per-GPU)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also report everything else: training AUC, instrumented steps "
+                         "(--instrument-steps) and the end-to-end fit (--fit-trees); a plain run only sets up, "
+                         "warms up, times the steps and prints the result line")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps save what they computed as DIR/<name>.npy (float32 / float64, under "
+                         "64 MB in all): tree models the margins of the training rows and the trees grown, dl-mlp "
+                         "the weights; same arguments = same inputs, so two builds can be compared file by file")
     ap.add_argument("--dump-trees", default="", help="tree models: rank 0 saves the trained trees (.npy)")
     ap.add_argument("--instrument-steps", type=int, default=-1,
                     help="tree models: extra steps measuring host enqueue / per-phase / collective time; "
-                         "-1 = 5 on GPU, 0 on CPU")
+                         "-1 = 5 with --full on GPU, else 0")
     ap.add_argument("--tree-graph", choices=["auto", "0", "1"], default="auto",
                     help="tree models: HIP-graph replay of each boosting step (H2OMX_TREE_GRAPH)")
     ap.add_argument("--loopback-ranks", type=int, default=0,
@@ -490,10 +558,10 @@ def main(argv=None) -> int:
     ap.add_argument("--seed", type=int, default=42)
     ap.add_argument("--device", choices=["auto", "cuda", "cpu"], default="auto",
                     help="cpu: the torch reference paths (multi-rank rehearsal of this script over gloo)")
-    ap.add_argument("--no-auc", action="store_true")
+    ap.add_argument("--no-auc", action="store_true", help="tree models: no training AUC even with --full")
     ap.add_argument("--fit-trees", type=int, default=-1,
                     help="tree models: also time a whole fit (sketch + binning + N trees + AUC) -> fit_rows_per_s; "
-                         "-1 = 50 on GPU, 0 on CPU")
+                         "-1 = 50 with --full on GPU, else 0")
     ap.add_argument("--oracle-rows", type=int, default=0,
                     help="also fit sklearn HistGradientBoosting on this many rows for AUC parity")
     args = ap.parse_args(argv)
@@ -518,7 +586,7 @@ def main(argv=None) -> int:
 
     device = args.device if args.device != "auto" else ("cuda" if torch.cuda.device_count() > 0 else "cpu")
     if args.instrument_steps < 0:
-        args.instrument_steps = 5 if device == "cuda" else 0
+        args.instrument_steps = 5 if args.full and device == "cuda" else 0
     comm = Comm.from_env(device)
     topo = None
     if comm.world_size > 1:

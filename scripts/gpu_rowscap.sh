@@ -6,6 +6,6 @@ mkdir -p gpurun_out
 export TMPDIR=/tmp
 python -m h2omx.build > gpurun_out/build.log 2>&1 || { echo BUILD FAILED; exit 1; }
 for RC in ${RCS:-32768 65536 131072 262144}; do
-  H2OMX_ROWS_CAP=$RC timeout -k 10 300 python bench.py --steps 50 --warmup 5 > gpurun_out/rc.json 2> gpurun_out/rc.err || { tail -5 gpurun_out/rc.err; exit 1; }
-  echo "RC=$RC $(python3 -c "import json; d=json.load(open('gpurun_out/rc.json')); print(d['ms_per_step'], d['train_auc'])")"
+  H2OMX_ROWS_CAP=$RC timeout -k 10 300 python bench.py --steps 50 --warmup 5 --full > $TMPDIR/rc.json 2> $TMPDIR/rc.err || { tail -5 $TMPDIR/rc.err; exit 1; }
+  echo "RC=$RC $(python3 -c "import json; d=json.load(open('$TMPDIR/rc.json')); print(d['ms_per_step'], d['train_auc'])")"
 done

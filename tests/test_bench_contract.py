@@ -27,7 +27,7 @@ def _run(nproc, extra, env_extra=None, timeout=600):
     env = dict(os.environ, OMP_NUM_THREADS="2", **(env_extra or {}))
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={nproc}",
            "--master-addr", "127.0.0.1", "--master-port", str(_port()), os.path.join(ROOT, "bench.py"),
-           "--gpus", str(nproc), "--steps", "2", "--warmup", "1"] + extra
+           "--gpus", str(nproc), "--steps", "2", "--warmup", "1", "--full"] + extra
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=timeout)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -52,6 +52,65 @@ def test_bench_two_ranks_cpu(model, extra):
         assert 0.6 < out["train_auc"] <= 1.0
     else:
         assert out["config"]["global_batch"] == 512
+
+
+def test_bench_plain_run_is_lean_and_dumps_its_outputs_cpu(tmp_path):
+    """Without ``--full`` the run reports the timed steps only (no AUC, no
+    instrumented steps, no end-to-end fit); ``--dump-outputs`` writes the
+    margins and trees of the timed path, identical from run to run."""
+    import numpy as np
+
+    outs = []
+    for d in ("a", "b"):
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+               "--device", "cpu", "--rows", "6000", "--dump-outputs", str(tmp_path / d)]
+        r = subprocess.run(cmd, cwd=ROOT, env=dict(os.environ, OMP_NUM_THREADS="2"), capture_output=True, text=True,
+                           timeout=300)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, r.stdout
+        outs.append(json.loads(lines[0]))
+    out = outs[0]
+    assert KEYS <= set(out)
+    assert out["steps"] == 3 and out["warmup"] == 1 and out["value"] > 0 and out["ms_per_step"] > 0
+    assert out["value"] == pytest.approx(6000 / (out["ms_per_step"] / 1000.0))
+    assert out["train_auc"] is None
+    assert not {"fit_rows_per_s", "phase_us_per_tree", "host_enqueue_us_per_tree"} & set(out)
+    assert sorted(os.listdir(tmp_path / "a")) == ["margin.npy", "trees.npy"]
+    for name in ("margin.npy", "trees.npy"):
+        a, b = np.load(tmp_path / "a" / name), np.load(tmp_path / "b" / name)
+        assert a.dtype in (np.float32, np.float64)
+        np.testing.assert_array_equal(a, b)
+    margin, trees = np.load(tmp_path / "a" / "margin.npy"), np.load(tmp_path / "a" / "trees.npy")
+    assert margin.shape == (6000,) and np.isfinite(margin).all() and margin.std() > 0
+    assert trees.shape[0] == 4 and trees.shape[2] == 6      # warm-up + timed trees
+    assert (trees[:, 0, 0] >= 0).all()                      # every root splits
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_dumps_the_hip_engines_outputs(tmp_path):
+    """HIP engine, plain run (graph replay, 4-tree groups): the dumped tree
+    table holds the reachable nodes of the trees ``--dump-trees`` saves and
+    zeros elsewhere, and there is one finite margin per training row."""
+    import numpy as np
+
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "6", "--warmup", "1",
+           "--rows", "100003", "--dump-outputs", str(tmp_path / "out"), "--dump-trees", str(tmp_path / "trees.npy")]
+    r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-3000:]
+    out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])
+    assert KEYS <= set(out) and out["graph_replay"] and out["train_auc"] is None
+    assert not {"fit_rows_per_s", "phase_us_per_tree"} & set(out)
+    margin, table = np.load(tmp_path / "out" / "margin.npy"), np.load(tmp_path / "out" / "trees.npy")
+    trees = np.load(tmp_path / "trees.npy")
+    assert margin.dtype == np.float32 and margin.shape == (100003,) and np.isfinite(margin).all()
+    assert table.dtype == np.float64 and table.shape == (7, trees.shape[1], 6)
+    for t in range(7):
+        keep = _reachable(trees[t])
+        for j, f in enumerate(("feat", "bin", "na_left", "value")):
+            np.testing.assert_array_equal(table[t, keep, j], trees[t][keep][f].astype(np.float64))
+        rest = np.setdiff1d(np.arange(trees.shape[1]), keep)
+        assert not table[t, rest].any()
 
 
 @pytest.mark.gpu

@@ -88,7 +88,7 @@ def _bench(nproc, extra, env_extra, timeout=300):
     env = dict(os.environ, OMP_NUM_THREADS="2", **env_extra)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={nproc}",
            "--master-addr", "127.0.0.1", "--master-port", str(_port()), os.path.join(ROOT, "bench.py"),
-           "--gpus", str(nproc), "--steps", "3", "--warmup", "1"] + extra
+           "--gpus", str(nproc), "--steps", "3", "--warmup", "1", "--full"] + extra
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=timeout)
     assert r.returncode == 0, r.stderr[-4000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
