@@ -542,6 +542,47 @@ struct GradFuse {
   GradParams gp;
 };
 
+// Level finalisation as the CONSUMER kernel's prologue (scan engine with fused
+// routing, one rank, levels of <= PRO_MAX_NODES nodes): instead of a
+// one-workgroup node_best_finalize launch between the level's split scan and
+// the kernel that routes its rows, every workgroup of that kernel recomputes
+// the level's decisions itself (level_prologue: node_best_wave + lf_decide +
+// lf_write_node, the same code and arithmetic as the launch, so every value
+// is bit-identical) and keeps the partition records in its own LDS.
+// Rules:
+//  * no workgroup ever waits for another - no ticket, flag, spin or
+//    cooperative launch; ordering comes only from kernel boundaries;
+//  * block 0 of the consuming launch is the writer: it alone stores the
+//    global results (nsplit, part, next_link, ctl_next, tree / leaf-children
+//    records, gbound, istate, treecat) for the launches after the boundary;
+//  * within the consuming launch nobody reads a location the writer stores
+//    (ctl_next, part, next_link, treecat, the children's gbound / istate):
+//    each workgroup uses its own copy, and a categorical record's local copy
+//    points at the scan's bitset (fbcat) instead of the tree's;
+//  * everything the prologue reads (fbest, the level's own ctl, the parents'
+//    gbound / istate, fbcat, edges, nvb) was written by earlier launches.
+struct FeatBest;
+constexpr int PRO_MAX_NODES = 64;
+struct LevelPro {
+  const FeatBest* fbest;   // nullptr: no prologue (the level was finalised by its own launch)
+  int* ctl_next;
+  const float* edges;
+  const int* nvb;
+  PartInfo* part;
+  NodeLink* next_link;
+  TreeNode* tree;
+  NodeSplit* nsplit;
+  int max_next_nodes;
+  int tree_capacity;
+  SplitParams p;
+};
+// (defined after level_finalize_body) finalises the level of control block
+// `ctl`: ps_s[0 .. n) = its partition records, returns the next level's slot
+// count (= ctl_next[CTL_SLOTS]; its node count is twice that) to every thread.
+// ns_s: PRO_MAX_NODES records of LDS scratch, res_s: one LDS int.
+__device__ __forceinline__ int level_prologue(const LevelPro& lp, const int* __restrict__ ctl, int nbt, bool writer,
+                                              NodeSplit* ns_s, PartInfo* ps_s, int* res_s);
+
 constexpr int CMP_STAGE_BYTES = 2048;   // per wave
 constexpr int HB_PF = 1;     // feature code loads kept in flight per lane
 
@@ -559,12 +600,23 @@ __global__ __launch_bounds__(1024) void hist_build_kernel(
     const int* __restrict__ nvb, const double* __restrict__ qscale, uint32_t salt, int F, int fg, int n_groups,
     int wgpg, int slot_lo, int slot_cnt, const short* __restrict__ slot16, unsigned long long* __restrict__ pk_buf,
     unsigned long long* __restrict__ partials, const PartInfo* __restrict__ part_prev,
-    const int* __restrict__ ctl_prev, int* __restrict__ nid_out, int writer, GradFuse gf) {
+    const int* __restrict__ ctl_prev, int* __restrict__ nid_out, int writer, GradFuse gf, LevelPro lp) {
   salt = (uint32_t)qscale[9];  // per-tree dither salt, written by tree_begin (graph-replay safe)
   extern __shared__ __attribute__((aligned(16))) unsigned long long lds64[];
   __shared__ int width_s[256], rep_s[256];
   __shared__ float rcp_s[256];
-  const int n_slots = ctl[CTL_SLOTS];
+  // ROUTE with a level prologue (LevelPro): the previous level is finalised
+  // here, by every workgroup for itself; its slot count and partition records
+  // come from that computation - `ctl` and `part_prev` are what block 0 WRITES
+  // in this launch and are not read
+  __shared__ NodeSplit pro_ns[ROUTE ? PRO_MAX_NODES : 1];
+  __shared__ PartInfo pro_ps[ROUTE ? PRO_MAX_NODES : 1];
+  __shared__ int pro_res;
+  bool pro = false;
+  if constexpr (ROUTE) pro = lp.fbest != nullptr;
+  int n_slots;
+  if (pro) n_slots = level_prologue(lp, ctl_prev, NBT, blockIdx.x == 0 && writer != 0, pro_ns, pro_ps, &pro_res);
+  else n_slots = ctl[CTL_SLOTS];
   const int b = blockIdx.x;
   const int xcd = b & 7, i = b >> 3;
   const int group = i % n_groups;
@@ -642,13 +694,13 @@ __global__ __launch_bounds__(1024) void hist_build_kernel(
       // one wave-uniform pass per previous-level node: its split feature's codes
       // for the lane's ROWS rows come in ONE coalesced load (no per-row byte
       // gathers); the host fuses only levels whose previous level has few nodes
-      const int n_prev = ctl_prev[CTL_N];
+      const int n_prev = pro ? min(ctl_prev[CTL_N], PRO_MAX_NODES) : ctl_prev[CTL_N];
       for (int j = 0; j < n_prev; ++j) {
         bool mine = false;
 #pragma unroll
         for (int k = 0; k < ROWS; ++k) mine |= (nn[k] == j);
         if (!mine) continue;
-        const PartInfo pj = part_prev[j];
+        const PartInfo pj = pro ? pro_ps[j] : part_prev[j];
         if (pj.child < 0) {
 #pragma unroll
           for (int k = 0; k < ROWS; ++k)
@@ -1938,10 +1990,15 @@ __device__ __forceinline__ void lf_write_node(int i, const NodeSplit& s, bool do
                                               int next_base, int max_next_nodes, const SplitParams& p,
                                               const float* __restrict__ edges, const int* __restrict__ nvb, int nbt,
                                               PartInfo* __restrict__ part, NodeLink* __restrict__ next_link,
-                                              TreeNode* __restrict__ tree, int tree_capacity) {
+                                              TreeNode* __restrict__ tree, int tree_capacity, bool writer = true,
+                                              PartInfo* local = nullptr) {
+  // writer = false (level prologue, every workgroup but the consumer launch's
+  // block 0): the same decisions and numbering, no global side effect; `local`
+  // receives the node's partition record (LDS copy of the calling workgroup)
   if (do_split && 2 * (k_idx + 1) > max_next_nodes) do_split = false;  // capacity guard
   const int gid = base + i;
-  const double v = clamp_bound(leaf_value(s.G, s.H, s.W, p), p, gid, tree_capacity);
+  const double v = writer ? clamp_bound(leaf_value(s.G, s.H, s.W, p), p, gid, tree_capacity) : 0.0;
+  const uint32_t* cat_src = nullptr;
   PartInfo pi;
   pi.gid = gid;
   pi.leaf_children = 0;
@@ -1954,15 +2011,20 @@ __device__ __forceinline__ void lf_write_node(int i, const NodeSplit& s, bool do
   if (do_split) {
     pi.feat = s.feat; pi.bin = s.bin; pi.na_left = s.na_left; pi.child = 2 * k_idx;
     tn.feat = s.feat; tn.bin = s.bin; tn.na_left = s.na_left; tn.left = next_base + 2 * k_idx;
-    const int m = nvb[s.feat];
-    tn.thr = (s.bin < m - 1) ? edges[(int64_t)s.feat * nbt + s.bin] : INFINITY;
+    if (writer) {
+      const int m = nvb[s.feat];
+      tn.thr = (s.bin < m - 1) ? edges[(int64_t)s.feat * nbt + s.bin] : INFINITY;
+    }
     if (p.catf != nullptr && p.catf[s.feat] && gid < tree_capacity) {
       // categorical group split: the (node, feature) scan's left-set bitset
       // becomes the tree's bitset of this node, and the partition record points at it
       const uint32_t* src = p.fbcat + ((int64_t)i * p.F + s.feat) * 8;
       uint32_t* dst = p.treecat + (int64_t)gid * 8;
+      if (writer) {
 #pragma unroll
-      for (int w = 0; w < 8; ++w) dst[w] = src[w];
+        for (int w = 0; w < 8; ++w) dst[w] = src[w];
+      }
+      cat_src = src;
       part_set_cat(pi, dst, s.na_left);
       tn.na_left = (s.na_left & 1) | 2;
       tn.thr = __int_as_float(0x7fc00000);   // NaN: not a threshold split
@@ -1975,14 +2037,14 @@ __device__ __forceinline__ void lf_write_node(int i, const NodeSplit& s, bool do
     L.sib_slot = build_left ? -1 : k_idx;
     R.slot = build_left ? -1 : k_idx;
     R.sib_slot = build_left ? k_idx : -1;
-    if (next_link) {
+    if (next_link && writer) {
       next_link[2 * k_idx] = L;
       next_link[2 * k_idx + 1] = R;
     }
     pi.pad = (L.slot & 0xFFFF) | (R.slot << 16);  // children's build slots (partition -> slot16)
     pi.child_gid = next_base + 2 * k_idx;
     const int cg = next_base + 2 * k_idx;
-    if (p.gbound != nullptr && cg + 1 < tree_capacity) {
+    if (writer && p.gbound != nullptr && cg + 1 < tree_capacity) {
       // monotone constraints: children inherit this node's interval; a split on a
       // constrained feature cuts it at the midpoint of the (clipped) child values
       double lo = -INFINITY, hi = INFINITY;
@@ -1998,10 +2060,11 @@ __device__ __forceinline__ void lf_write_node(int i, const NodeSplit& s, bool do
       p.gbound[2 * cg] = llo; p.gbound[2 * cg + 1] = lhi;
       p.gbound[2 * cg + 2] = rlo; p.gbound[2 * cg + 3] = rhi;
     }
-    if (p.istate != nullptr && cg + 1 < tree_capacity && gid < tree_capacity) inter_children(p, gid, s.feat, cg);
-    if (p.children_leaves) {
+    if (writer && p.istate != nullptr && cg + 1 < tree_capacity && gid < tree_capacity)
+      inter_children(p, gid, s.feat, cg);
+    if (p.children_leaves) pi.leaf_children = 1;
+    if (writer && p.children_leaves) {
       // children are final: their totals come from this split's left stats
-      pi.leaf_children = 1;
       const double GR = s.G - s.GL, HR = s.H - s.HL, WR = s.W - s.WL;
       TreeNode lc, rc;
       lc.feat = rc.feat = -1;
@@ -2023,8 +2086,17 @@ __device__ __forceinline__ void lf_write_node(int i, const NodeSplit& s, bool do
     pi.feat = -1; pi.bin = 0; pi.na_left = 0; pi.child = -1;
     tn.feat = -1; tn.bin = 0; tn.na_left = 0; tn.left = -1; tn.thr = 0.0f;
   }
-  part[i] = pi;
-  if (gid < tree_capacity) tree[gid] = tn;
+  if (writer) {
+    part[i] = pi;
+    if (gid < tree_capacity) tree[gid] = tn;
+  }
+  if (local) {
+    // the local copy of a categorical split tests the scan's bitset (written by
+    // an earlier launch, same bits) - never the tree's copy, which the writer
+    // workgroup stores during this launch
+    if (cat_src) part_set_cat(pi, cat_src, s.na_left);
+    *local = pi;
+  }
 }
 
 __device__ __forceinline__ void lf_write_ctl(int* __restrict__ ctl_next, int ks, int next_base, int max_next_nodes) {
@@ -2196,6 +2268,50 @@ __global__ __launch_bounds__(1024) void node_best_finalize_kernel(
                       tree_capacity);
 }
 
+// The same finalisation as node_best_finalize_kernel for a level of
+// n <= PRO_MAX_NODES nodes, run by EVERY workgroup of the consumer launch (see
+// LevelPro for the rules): the waves take the nodes round-robin (records into
+// LDS), wave 0 decides and numbers the level in one ballot (one 64-node chunk
+// of level_finalize_body: carry = 0, no earlier wave).  writer: also store
+// the global results.  Called by all threads of the workgroup.
+__device__ __forceinline__ int level_prologue(const LevelPro& lp, const int* __restrict__ ctl, int nbt, bool writer,
+                                              NodeSplit* ns_s, PartInfo* ps_s, int* res_s) {
+  const SplitParams& p = lp.p;
+  const int n = min(ctl[CTL_N], PRO_MAX_NODES);   // the host sends only levels that fit
+  const int base = ctl[CTL_BASE];
+  const int next_base = base + n;
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, nw = blockDim.x >> 6;
+  // (loading every feature's whole record for several nodes in one round, the
+  // winner's fields by readlane, measured slower than this per-node chain:
+  // profiles/r7/fin_prologue_ab.txt)
+  for (int node = wid; node < n; node += nw) {
+    node_best_wave(lp.fbest, p.F, node, lane, ns_s);
+    if (writer && lane == 0) lp.nsplit[node] = ns_s[node];
+  }
+  __syncthreads();
+  if (wid == 0) {
+    const int i = lane;
+    bool do_split = false;
+    NodeSplit s;
+    if (i < n) {
+      s = ns_s[i];
+      do_split = lf_decide(s, p);
+    }
+    const unsigned long long bal = __ballot(do_split);
+    if (i < n)
+      lf_write_node(i, s, do_split, __popcll(bal & ((1ull << lane) - 1ull)), base, next_base, lp.max_next_nodes, p,
+                    lp.edges, lp.nvb, nbt, lp.part, lp.next_link, lp.tree, lp.tree_capacity, writer, ps_s + i);
+    if (lane == 0) {
+      int ks = __popcll(bal);
+      if (writer) lf_write_ctl(lp.ctl_next, ks, next_base, lp.max_next_nodes);
+      if (2 * ks > lp.max_next_nodes) ks = lp.max_next_nodes / 2;   // as lf_write_ctl
+      *res_s = ks;
+    }
+  }
+  __syncthreads();
+  return *res_s;
+}
+
 // N ranks (after reduce_split_p2p): wait for every rank's done word, then the
 // same per-node arg-max over the all-gathered split table + finalisation.
 // Identical records on every rank -> identical trees.
@@ -2272,20 +2388,30 @@ __global__ __launch_bounds__(256) void partition_kernel(const uint8_t* __restric
                                                         const int* __restrict__ ctl_next, int win_max, int R,
                                                         short* __restrict__ slot16, int* nid_out, int all_rows,
                                                         const float* __restrict__ Fm, const float* __restrict__ yv,
-                                                        GradParams gp, const uint8_t* __restrict__ y8) {
+                                                        GradParams gp, const uint8_t* __restrict__ y8,
+                                                        LevelPro lp) {
   extern __shared__ __attribute__((aligned(16))) unsigned long long lacc[];
   __shared__ PartInfo ps[PART_LDS_NODES];
+  // level prologue (LevelPro): this level is finalised here, by every
+  // workgroup for itself - ps[] and the next level's node count come from that
+  // computation; `part` and `ctl_next` are what block 0 WRITES in this launch
+  // and are not read
+  __shared__ NodeSplit pro_ns[PRO_MAX_NODES];
+  __shared__ int pro_res;
+  const bool pro = lp.fbest != nullptr;
+  int n_next = 0;
+  if (pro) n_next = 2 * level_prologue(lp, ctl_cur, nbt, blockIdx.x == 0, pro_ns, ps, &pro_res);
   const bool use_lds = leaf_acc != nullptr && win_max > 0;
   // all_rows (final level of the fused-routing pipeline): rows that retired at
   // earlier levels (nid = ~gid) add their sums here too; the LDS window is the
   // whole tree [0, win_max)
   const int base = all_rows ? 0 : ctl_cur[CTL_BASE];
-  const int win = use_lds ? (all_rows ? win_max : min(win_max, ctl_cur[CTL_N] + ctl_next[CTL_N])) : 0;
+  const int win = use_lds ? (all_rows ? win_max : min(win_max, ctl_cur[CTL_N] + (pro ? n_next : ctl_next[CTL_N]))) : 0;
   // the level's split records: LDS-staged when they fit (the node id -> split
   // record -> split code chain then has one dependent global load, not two)
   const int n_cur = ctl_cur[CTL_N];
-  const bool rec_lds = n_cur <= PART_LDS_NODES;   // split records staged in LDS
-  if (rec_lds)
+  const bool rec_lds = pro || n_cur <= PART_LDS_NODES;   // split records staged in LDS
+  if (rec_lds && !pro)
     for (int j = threadIdx.x; j < n_cur; j += blockDim.x) ps[j] = part[j];
   if (use_lds)
     for (int j = threadIdx.x; j < 3 * win * R; j += blockDim.x) lacc[j] = 0ull;
@@ -3078,15 +3204,37 @@ H2OMX_API int h2omx_bin_features(const float* X, int64_t ld, int64_t n, int F, c
   return launch_status();
 }
 
+// Level prologue arguments (LevelPro): the finalisation's inputs and outputs,
+// exactly those of h2omx_level_finalize for the same level.
+static bool make_pro(LevelPro& lp, const void* fbest, const void* params, int* ctl_next, const float* edges,
+                     const int* nvb, int max_next_nodes, void* part, void* next_link, void* tree, int tree_capacity,
+                     void* nsplit, int max_nodes) {
+  if (fbest == nullptr || params == nullptr || ctl_next == nullptr || nvb == nullptr || part == nullptr ||
+      tree == nullptr || nsplit == nullptr || max_nodes < 1 || max_nodes > PRO_MAX_NODES)
+    return false;
+  lp.fbest = reinterpret_cast<const FeatBest*>(fbest);
+  lp.ctl_next = ctl_next; lp.edges = edges; lp.nvb = nvb; lp.part = reinterpret_cast<PartInfo*>(part);
+  lp.next_link = reinterpret_cast<NodeLink*>(next_link); lp.tree = reinterpret_cast<TreeNode*>(tree);
+  lp.nsplit = reinterpret_cast<NodeSplit*>(nsplit);
+  lp.max_next_nodes = max_next_nodes; lp.tree_capacity = tree_capacity;
+  lp.p = *reinterpret_cast<const SplitParams*>(params);
+  return true;
+}
+
 static int hist_build_launch(const uint8_t* codes, int64_t npad, const float* g, const float* s2, const int* nid,
                              const void* link, const int* ctl, const int* nvb, const double* qscale, int salt,
                              int F, int nbt, int fg, int n_groups, int wgpg, int slot_lo, int slot_cnt,
                              int rows_per_lane, int threads, const short* slot16, unsigned long long* pk_buf,
                              int pkm, unsigned long long* partials, const void* part_prev, const int* ctl_prev,
-                             int* nid_out, int writer, hipStream_t stream, const GradFuse* gfp = nullptr) {
+                             int* nid_out, int writer, hipStream_t stream, const GradFuse* gfp = nullptr,
+                             const LevelPro* lpp = nullptr) {
   const bool route = part_prev != nullptr;
   GradFuse gfz{};
   if (gfp) gfz = *gfp;
+  // level prologue: the previous level is finalised inside this (routing, writer) launch
+  LevelPro lpz{};
+  if (lpp) lpz = *lpp;
+  if (lpp && (!route || !writer || lpz.fbest == nullptr || lpz.nsplit == nullptr)) return kBadArg;
   // pkm bit 3: wave-compacted atomics (CMP; stored rows, 16-row units, <= 64 slots per pass)
   const bool cmp = (pkm & 8) != 0;
   // pkm bit 4 / 5: level-0 histograms in 8 / 4 interleaved lane copies (PKM 1 / 3 only)
@@ -3121,15 +3269,15 @@ static int hist_build_launch(const uint8_t* codes, int64_t npad, const float* g,
 #define LAUNCH_HBK(NB, R, M, RT, C)                                                                           \
   hipLaunchKernelGGL((hist_build_kernel<NB, R, M, RT, C>), dim3(grid), dim3(threads), lds, stream, codes, npad, \
                      g, s2, nid, lk, ctl, nvb, qscale, (uint32_t)salt, F, fg, n_groups, wgpg, slot_lo, slot_cnt,  \
-                     slot16, pk_buf, partials, pp, ctl_prev, nid_out, writer, gfz)
+                     slot16, pk_buf, partials, pp, ctl_prev, nid_out, writer, gfz, lpz)
 #define LAUNCH_HBKC(NB, R, M, CP)                                                                                \
   hipLaunchKernelGGL((hist_build_kernel<NB, R, M, false, false, CP>), dim3(grid), dim3(threads), lds, stream, codes, \
                      npad, g, s2, nid, lk, ctl, nvb, qscale, (uint32_t)salt, F, fg, n_groups, wgpg, slot_lo,        \
-                     slot_cnt, slot16, pk_buf, partials, pp, ctl_prev, nid_out, writer, gfz)
+                     slot_cnt, slot16, pk_buf, partials, pp, ctl_prev, nid_out, writer, gfz, lpz)
 #define LAUNCH_HBK16(NB, M)                                                                                      \
   hipLaunchKernelGGL((hist_build_kernel<NB, 16, M, true, false, 1, true>), dim3(grid), dim3(threads), lds, stream, \
                      codes, npad, g, s2, nid, lk, ctl, nvb, qscale, (uint32_t)salt, F, fg, n_groups, wgpg, slot_lo,    \
-                     slot_cnt, slot16, pk_buf, partials, pp, ctl_prev, nid_out, writer, gfz)
+                     slot_cnt, slot16, pk_buf, partials, pp, ctl_prev, nid_out, writer, gfz, lpz)
 #define LAUNCH_HB(NB, R)                                            \
   do {                                                             \
     if (pkm == 0) LAUNCH_HBK(NB, R, 0, false, false);               \
@@ -3238,6 +3386,27 @@ H2OMX_API int h2omx_hist_build_route(const uint8_t* codes, int64_t npad, const i
   return hist_build_launch(codes, npad, nullptr, nullptr, nid_prev, nullptr, ctl, nvb, qscale, 0, F, nbt, fg, n_groups,
                            wgpg, slot_lo, slot_cnt, rows_per_lane, threads, nullptr, pk_buf, pkm, partials, part_prev,
                            ctl_prev, nid_out, writer, stream);
+}
+
+// h2omx_hist_build_route that also finalises the previous level (level
+// prologue, LevelPro) - replaces h2omx_level_finalize + h2omx_hist_build_route
+// for one-pass levels whose previous level holds <= 64 nodes.  ctl_prev is that
+// level's control block; `ctl` (its ctl_next), part_prev (its part), next_link,
+// tree and nsplit are written by block 0.
+H2OMX_API int h2omx_hist_build_route_fin(const uint8_t* codes, int64_t npad, const int* nid_prev, void* part_prev,
+                                         const int* ctl_prev, int* nid_out, int* ctl, const int* nvb,
+                                         const double* qscale, int F, int nbt, int fg, int n_groups, int wgpg,
+                                         int slot_cnt, int rows_per_lane, int threads, unsigned long long* pk_buf,
+                                         int pkm, unsigned long long* partials, const void* fbest, const void* params,
+                                         const float* edges, int max_next_nodes, void* next_link, void* tree,
+                                         int tree_capacity, void* nsplit, int max_nodes, hipStream_t stream) {
+  LevelPro lp{};
+  if (!make_pro(lp, fbest, params, ctl, edges, nvb, max_next_nodes, part_prev, next_link, tree, tree_capacity, nsplit,
+                max_nodes))
+    return kBadArg;
+  return hist_build_launch(codes, npad, nullptr, nullptr, nid_prev, nullptr, ctl, nvb, qscale, 0, F, nbt, fg, n_groups,
+                           wgpg, 0, slot_cnt, rows_per_lane, threads, nullptr, pk_buf, pkm, partials, part_prev,
+                           ctl_prev, nid_out, 1, stream, nullptr, &lp);
 }
 
 H2OMX_API int h2omx_hist_reduce(const unsigned long long* partials, int n_groups, int wgpg, int fg, int F, int nbt,
@@ -3476,7 +3645,12 @@ static int partition_launch(const uint8_t* codes, int64_t npad, int* nid, const 
                             unsigned long long* leaf_acc, const int* ctl_cur, const int* ctl_next, int win_max,
                             int blocks, int prefetch, short* slot16, int* nid_out, int all_rows, hipStream_t stream,
                             const float* Fm = nullptr, const float* yv = nullptr, const GradParams* gpp = nullptr,
-                            int nidm = 0, const uint8_t* y8 = nullptr) {
+                            int nidm = 0, const uint8_t* y8 = nullptr, const LevelPro* lpp = nullptr) {
+  // level prologue: this level is finalised inside the launch (ctl_next / part are then outputs)
+  LevelPro lpz{};
+  if (lpp) lpz = *lpp;
+  if (lpp && (lpz.fbest == nullptr || lpz.nsplit == nullptr || lpz.ctl_next != ctl_next || (const void*)lpz.part != part))
+    return kBadArg;
   // nidm bit 0: nid is an int16 stream, bit 1: nid_out is (fused pipeline; distinct buffers)
   if (nidm != 0 && nid_out == nid) return kBadArg;
   GradParams gp{};
@@ -3500,7 +3674,7 @@ static int partition_launch(const uint8_t* codes, int64_t npad, int* nid, const 
 #define LAUNCH_PK(PF, NM, WIN)                                                                                  \
   hipLaunchKernelGGL((partition_kernel<PF, PART_RPL, NM>), dim3(blocks), dim3(256), lds, stream, codes, npad, nid, \
                      reinterpret_cast<const PartInfo*>(part), nbt, g, h, w, qscale, cap, leaf_acc, ctl_cur,        \
-                     ctl_next, WIN, R, slot16, nid_out, all_rows, Fm, yv, gp, y8)
+                     ctl_next, WIN, R, slot16, nid_out, all_rows, Fm, yv, gp, y8, lpz)
   if (prefetch && leaf_acc) {
     if (nidm == 3) LAUNCH_PK(true, 3, win_max);
     else if (nidm & 1) LAUNCH_PK(true, 1, win_max);
@@ -3548,6 +3722,41 @@ H2OMX_API int h2omx_partition_final(const uint8_t* codes, int64_t npad, const in
   return partition_launch(codes, npad, const_cast<int*>(nid_in), part, nbt, g, h, w, qscale, cap, leaf_acc, ctl_cur,
                           ctl_next, cap, blocks, 1, nullptr, nid_out, 1, stream, Fm, y,
                           reinterpret_cast<const GradParams*>(gparams), nidm, y8);
+}
+
+// h2omx_partition_route / h2omx_partition_final that also finalise the level
+// they route (level prologue, LevelPro) - each replaces h2omx_level_finalize +
+// the partition for levels of <= 64 nodes.  part and ctl_next are written by
+// block 0.
+H2OMX_API int h2omx_partition_route_fin(const uint8_t* codes, int64_t npad, const int* nid_in, int* nid_out, void* part,
+                                        int nbt, const int* ctl_cur, int* ctl_next, int blocks, short* slot16,
+                                        int nidm, const void* fbest, const void* params, const float* edges,
+                                        const int* nvb, int max_next_nodes, void* next_link, void* tree,
+                                        int tree_capacity, void* nsplit, int max_nodes, hipStream_t stream) {
+  if (slot16 == nullptr) return kBadArg;
+  LevelPro lp{};
+  if (!make_pro(lp, fbest, params, ctl_next, edges, nvb, max_next_nodes, part, next_link, tree, tree_capacity, nsplit,
+                max_nodes))
+    return kBadArg;
+  return partition_launch(codes, npad, const_cast<int*>(nid_in), part, nbt, nullptr, nullptr, nullptr, nullptr, 0,
+                          nullptr, ctl_cur, ctl_next, 0, blocks, 0, slot16, nid_out, 0, stream, nullptr, nullptr,
+                          nullptr, nidm, nullptr, &lp);
+}
+
+H2OMX_API int h2omx_partition_final_fin(const uint8_t* codes, int64_t npad, const int* nid_in, int* nid_out, void* part,
+                                        int nbt, const float* g, const float* h, const float* w, const double* qscale,
+                                        int cap, unsigned long long* leaf_acc, const int* ctl_cur, int* ctl_next,
+                                        int blocks, const float* Fm, const float* y, const void* gparams, int nidm,
+                                        const uint8_t* y8, const void* fbest, const void* params, const float* edges,
+                                        const int* nvb, int max_next_nodes, void* next_link, void* tree,
+                                        int tree_capacity, void* nsplit, int max_nodes, hipStream_t stream) {
+  LevelPro lp{};
+  if (!make_pro(lp, fbest, params, ctl_next, edges, nvb, max_next_nodes, part, next_link, tree, tree_capacity, nsplit,
+                max_nodes))
+    return kBadArg;
+  return partition_launch(codes, npad, const_cast<int*>(nid_in), part, nbt, g, h, w, qscale, cap, leaf_acc, ctl_cur,
+                          ctl_next, cap, blocks, 1, nullptr, nid_out, 1, stream, Fm, y,
+                          reinterpret_cast<const GradParams*>(gparams), nidm, y8, &lp);
 }
 
 static inline int stream_grid(int64_t) { return STAT_BLOCKS; }

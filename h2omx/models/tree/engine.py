@@ -156,6 +156,16 @@ class HipTreeBuilder:
     # so the single-rank level keeps the separate finalisation launch
     FUSE_FIN = True
     FUSE_FIN_LOCAL = False
+    # one rank, scan engine with fused routing, one-pass levels of <= 64 nodes: no
+    # finalisation launch - every workgroup of the kernel that routes the level's
+    # rows (the next level's routed histogram, partition_route or partition_final)
+    # finalises it for itself in a prologue and block 0 stores the results
+    # (LevelPro in csrc/tree_kernels.hip; profiles/r7/fin_prologue_ab.txt).
+    # False: the node_best_finalize launch per level.  The last level keeps its
+    # launch: 1024 partition_final workgroups start 7.0 us later behind the
+    # prologue, the launch costs 5.9 us (FIN_PROLOGUE_FINAL = True moves it too)
+    FIN_PROLOGUE = True
+    FIN_PROLOGUE_FINAL = False
     # segmented engine: part_scatter moves each row's (g, s2) into segment order with it
     PERMUTE_GS = True
     # direct levels of <= 16 eligible features store them per row for the partition
@@ -546,6 +556,7 @@ class HipTreeBuilder:
         nid16 = self.nid16 is not None
         nid_buf = self.nid16 if nid16 else (self.nid, self.nid2)
         part_prev = None
+        pend = None    # level d - 1's finalisation, left to level d's routed histogram (FIN_PROLOGUE)
         for d in range(max_depth):
             cur, nxt = d % 2, (d + 1) % 2
             ctl_cur, ctl_nxt = self.ctl[cur], self.ctl[nxt]
@@ -599,6 +610,17 @@ class HipTreeBuilder:
                 self._fin_ticket = torch.zeros((1,), dtype=torch.int32, device=self.dev)   # each launch leaves 0
             fin_args = (P(ctl_nxt), P(bm.edges), next_nodes, P(part), P(nl), P(self.tree_buf), self.capacity,
                         P(nsplit), P(self._fin_ticket if fin else None))
+            # the level is finalised in the prologue of the launch that routes its rows:
+            # "hist" (level d + 1's routed histogram, one pass), "route" or "final"
+            pro = None
+            if (self.FIN_PROLOGUE and comm is None and fuse and not fin and plan["passes"] == 1
+                    and max_nodes <= 64):
+                if last:
+                    pro = "final" if self.FIN_PROLOGUE_FINAL else None
+                elif not self._fused_level(d + 1):
+                    pro = "route"
+                elif self.plan_level(max(1, next_nodes // 2))["passes"] == 1:
+                    pro = "hist"
 
             def reduce(n_groups, wgpg, fg, slot_lo, slot_cnt):
                 if rs and fuse_p2p:
@@ -635,7 +657,17 @@ class HipTreeBuilder:
             for ps in range(plan["passes"]):
                 slot_lo = ps * plan["slot_cnt"]
                 with T("hist"):
-                    if d > 0 and fuse and self._fused_level(d):
+                    if d > 0 and pend is not None:
+                        # level d - 1 is finalised AND routed in here: nid_buf[d - 1] -> nid_buf[d]
+                        ops.check(lib.h2omx_hist_build_route_fin(
+                            P(bm.codes), bm.npad, P(None if (d == 1 and self.implicit_root) else nid_buf[(d - 1) % 2]),
+                            P(part_prev), P(ctl_nxt), P(nid_buf[d % 2]), P(ctl_cur), P(bm.nvb), P(self.qscale),
+                            F, nbt, plan["fg"], plan["n_groups"], plan["wgpg"], plan["slot_cnt"],
+                            self.ROWS_PER_LANE, plan["threads"], P(self.pk),
+                            (4 if self.pk32 else 2) + (64 if nid16 else 0), P(partials), *pend["args"], st),
+                            "hist_build_route_fin")
+                        pend = None
+                    elif d > 0 and fuse and self._fused_level(d):
                         # partition of level d - 1 fused in: nid_buf[d - 1] -> nid_buf[d]
                         ops.check(lib.h2omx_hist_build_route(
                             P(bm.codes), bm.npad, P(None if (d == 1 and self.implicit_root) else nid_buf[(d - 1) % 2]),
@@ -682,6 +714,15 @@ class HipTreeBuilder:
                                                    max_nodes, nbt, P(fbest), st), "split_find")
                 if fin:
                     pass   # finalised inside the reduce launch
+                elif pro is not None:
+                    # finalised by the launch that routes this level (a snapshot of the
+                    # level's SplitParams and its buffers travel to the next iteration)
+                    spc = type(sp).from_buffer_copy(sp)
+                    pro_tail = (P(fbest), ctypes.addressof(spc), P(bm.edges))
+                    pro_rest = (next_nodes, P(nl), P(self.tree_buf), self.capacity, P(nsplit), max_nodes)
+                    if pro == "hist":
+                        pend = dict(args=pro_tail + pro_rest,
+                                    keep=(spc, fbest, nl, nsplit, self._bufs.get("fbcat")))
                 elif fuse_p2p:
                     # waits for every rank's share of the split records (all-gathered
                     # into this rank's split table by reduce_split_p2p)
@@ -704,22 +745,28 @@ class HipTreeBuilder:
                     # for boost_update; otherwise int32 into self.nid
                     leaf16 = chain and nid16
                     self.leaf16_buf = nid_buf[(d + 1) % 2] if leaf16 else None
-                    ops.check(lib.h2omx_partition_final(P(bm.codes), bm.npad, P(nid_buf[d % 2]),
-                                                        P(self.leaf16_buf if leaf16 else self.nid),
-                                                        P(part), nbt, P(g), P(h), P(w), P(self.qscale),
-                                                        self.capacity, P(self.leaf_acc), P(ctl_cur), P(ctl_nxt),
-                                                        self.part_blocks, P(rg[0] if rg else None),
-                                                        P(rg[1] if rg else None),
-                                                        ctypes.addressof(rg[2]) if rg else None,
-                                                        (3 if leaf16 else 1) if nid16 else 0,
-                                                        P(rg[3] if rg else None), st),
-                              "partition_final")
+                    pf_args = (P(bm.codes), bm.npad, P(nid_buf[d % 2]),
+                               P(self.leaf16_buf if leaf16 else self.nid),
+                               P(part), nbt, P(g), P(h), P(w), P(self.qscale),
+                               self.capacity, P(self.leaf_acc), P(ctl_cur), P(ctl_nxt),
+                               self.part_blocks, P(rg[0] if rg else None),
+                               P(rg[1] if rg else None),
+                               ctypes.addressof(rg[2]) if rg else None,
+                               (3 if leaf16 else 1) if nid16 else 0,
+                               P(rg[3] if rg else None))
+                    if pro == "final":
+                        ops.check(lib.h2omx_partition_final_fin(*pf_args, *pro_tail, P(bm.nvb), *pro_rest, st),
+                                  "partition_final_fin")
+                    else:
+                        ops.check(lib.h2omx_partition_final(*pf_args, st), "partition_final")
                 elif fuse and not self._fused_level(d + 1):
-                    ops.check(lib.h2omx_partition_route(P(bm.codes), bm.npad, P(nid_buf[d % 2]),
-                                                        P(nid_buf[(d + 1) % 2]), P(part), nbt, P(ctl_cur),
-                                                        P(ctl_nxt), self.part_blocks, P(self.slot16),
-                                                        3 if nid16 else 0, st),
-                              "partition_route")
+                    pr_args = (P(bm.codes), bm.npad, P(nid_buf[d % 2]), P(nid_buf[(d + 1) % 2]), P(part), nbt,
+                               P(ctl_cur), P(ctl_nxt), self.part_blocks, P(self.slot16), 3 if nid16 else 0)
+                    if pro == "route":
+                        ops.check(lib.h2omx_partition_route_fin(*pr_args, *pro_tail, P(bm.nvb), *pro_rest, st),
+                                  "partition_route_fin")
+                    else:
+                        ops.check(lib.h2omx_partition_route(*pr_args, st), "partition_route")
                 elif not fuse:
                     ops.check(lib.h2omx_partition(P(bm.codes), bm.npad, P(self.nid), P(part), nbt, P(g), P(h),
                                                   P(w), P(self.qscale), self.capacity, P(self.leaf_acc),

@@ -33,6 +33,11 @@ TREE_SIGS = {
     "h2omx_partition_blocks": "",
     "h2omx_partition_final": "PLPPPIPPPPIPPPIPPPIPS",
     "h2omx_partition_route": "PLPPPIPPIPIS",
+    # level finalisation as the consumer launch's prologue (+ fbest, params, edges,
+    # [nvb,] max_next_nodes, next_link, tree, tree_capacity, nsplit, max_nodes)
+    "h2omx_hist_build_route_fin": "PLPPPPPPPIIIIIIIIPIPPPPIPPIPIS",
+    "h2omx_partition_route_fin": "PLPPPIPPIPIPPPPIPPIPIS",
+    "h2omx_partition_final_fin": "PLPPPIPPPPIPPPIPPPIPPPPPIPPIPIS",
     "h2omx_leaf_reduce": "PIIPS",
     "h2omx_boost_update": "PPPLLPPPPPPPLPIPIPPIIPPS",
     "h2omx_apply_tree": "PLPPS",
