@@ -88,7 +88,7 @@ struct SplitParams {
   int pad3;
 };
 
-struct NodeSplit {  // best split of one node at the current level (64 B)
+struct NodeSplit {  // best split of one node at the current level (72 B)
   double gain;
   double G, H, W;      // node totals
   double GL, HL, WL;   // left-child totals of the chosen split
@@ -542,6 +542,290 @@ struct GradFuse {
   GradParams gp;
 };
 
+// ---------------------------------------------------------------------------
+// Level finalisation: the split records of a level (FeatBest per (node,
+// feature), written by the split scans of K4 + K5 below), the per-node
+// arg-max over them, and the decisions that close the level - in dependency
+// order, ahead of every kernel that runs them.
+// ---------------------------------------------------------------------------
+struct FeatBest {  // 64 B
+  double gain;
+  double GL, SL;   // left-child totals of the chosen threshold
+  double G, S;     // node totals (as seen from this feature's histogram)
+  double pad0;
+  int code;        // (bin * 2 + na_left), INT_MAX = none
+  int pad1;
+  double pad2;
+};
+
+// Best threshold of (node, f) computed by one wave; every lane returns the
+// same result (gain -inf / code INT_MAX = none).  Also stores the completed
+// histogram row into `full` (parent of the next level) when given.
+struct WaveBest {
+  double gain, GL, SL, G, S;
+  int code;
+};
+
+__device__ __forceinline__ void store_feat_best(FeatBest* __restrict__ out, int64_t i, const WaveBest& w) {
+  FeatBest r{};
+  r.gain = w.gain; r.GL = w.GL; r.SL = w.SL;
+  r.G = w.G; r.S = w.S;
+  r.code = w.code;
+  out[i] = r;
+}
+
+__device__ __forceinline__ void store_feat_best_wt(FeatBest* __restrict__ out, int64_t i, const WaveBest& w) {
+  FeatBest* d = out + i;
+  __hip_atomic_store(&d->gain, w.gain, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  __hip_atomic_store(&d->GL, w.GL, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  __hip_atomic_store(&d->SL, w.SL, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  __hip_atomic_store(&d->G, w.G, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  __hip_atomic_store(&d->S, w.S, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  __hip_atomic_store(reinterpret_cast<long long*>(&d->code), (long long)(uint32_t)w.code, __ATOMIC_RELAXED,
+                     __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// Per-node arg-max over the features' best thresholds (gain desc, then
+// feature / bin / NA-direction asc): one wave per node, lane = feature.
+// MODE 0: plain loads (records of an earlier launch); 1: written by other
+// workgroups of this launch (agent-scope `sc1` loads); 2: pushed by peer ranks
+// (N-rank split table, system-scope loads; p2p_device.h)
+template <int MODE>
+__device__ __forceinline__ double fb_ld(const double* p) {
+  if constexpr (MODE == 2) return p2pdev::ld_sys(p);
+  else if constexpr (MODE == 1) return __hip_atomic_load(const_cast<double*>(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  else return *p;
+}
+template <int MODE>
+__device__ __forceinline__ int fb_code(const FeatBest* r) {
+  const uint32_t* c = reinterpret_cast<const uint32_t*>(&r->code);
+  if constexpr (MODE == 2) return (int)p2pdev::ld_sys(c);
+  else if constexpr (MODE == 1) return (int)__hip_atomic_load(const_cast<uint32_t*>(c), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  else return r->code;
+}
+
+template <int SYS = 0>
+__device__ __forceinline__ void node_best_wave(const FeatBest* __restrict__ fbest, int F, int node, int lane,
+                                               NodeSplit* __restrict__ out) {
+  const FeatBest* fb = fbest + (int64_t)node * F;
+  double bg = -INFINITY;
+  long long key = 0x7fffffffffffffffLL;  // (feature, code) order for ties
+  int bf = -1;
+  for (int f = lane; f < F; f += 64) {
+    const double gn = fb_ld<SYS>(&fb[f].gain);
+    const int code = fb_code<SYS>(&fb[f]);
+    if (code == 0x7fffffff || !(gn > -INFINITY)) continue;
+    const long long k = ((long long)f << 32) | (unsigned)code;
+    if (bf < 0 || gn > bg || (gn == bg && k < key)) { bg = gn; key = k; bf = f; }
+  }
+  wave_argmax_key(bg, key);
+  if (lane == 0) {
+    NodeSplit s;
+    // S is W (mode 0) or H (mode 1); exact leaf (G, H, W) sums come from the
+    // partition kernels, these only steer the split decisions
+    s.G = fb_ld<SYS>(&fb[0].G); s.H = fb_ld<SYS>(&fb[0].S); s.W = s.H;
+    s.pad = 0;
+    if (key != 0x7fffffffffffffffLL) {
+      const int f = (int)(key >> 32), code = (int)(key & 0xffffffff);
+      const FeatBest& c = fb[f];
+      s.gain = fb_ld<SYS>(&c.gain); s.GL = fb_ld<SYS>(&c.GL); s.HL = fb_ld<SYS>(&c.SL); s.WL = s.HL;
+      s.feat = f; s.bin = code >> 1; s.na_left = code & 1;
+    } else {
+      s.gain = -INFINITY; s.GL = s.HL = s.WL = 0.0;
+      s.feat = -1; s.bin = 0; s.na_left = 0;
+    }
+    out[node] = s;
+  }
+}
+
+// Where a level's finalisation writes, and the sizes that go with it - the
+// same record for every path that finalises a level (its own launch, the last
+// workgroup of the reduce + split scan, the consumer kernel's prologue).
+// Mirrored by LevelOut in models/tree/structs.py.
+struct LevelOut {
+  int* ctl_next;         // the next level's control block
+  const float* edges;    // [F][nbt] cut points (tree thresholds)
+  const int* nvb;        // [F] valid bins
+  PartInfo* part;        // [max_nodes] routing records of this level
+  NodeLink* next_link;   // [max_next_nodes] histogram sources of the next level (nullptr: last level)
+  TreeNode* tree;        // [tree_capacity]
+  NodeSplit* nsplit;     // [max_nodes] the level's per-node split records
+  int max_next_nodes;
+  int tree_capacity;
+};
+
+// ---------------------------------------------------------------------------
+// Level finalisation (single workgroup): decide split/leaf per node, number
+// the children, pick the smaller child to build, write tree records and the
+// partition table.  ctl_next receives the next level's counts.
+// ---------------------------------------------------------------------------
+__device__ __forceinline__ bool lf_decide(const NodeSplit& s, const SplitParams& p) {
+  bool do_split = !p.is_last_level && s.feat >= 0 && isfinite(s.gain) && s.gain > 0.0;
+  if (do_split && p.mode == 0 && p.min_split_improvement > 0.0) {
+    // relative improvement over the node's explained sum of squares
+    const double base_term = (s.W > 0.0) ? s.G * s.G / s.W : 0.0;
+    do_split = s.gain > p.min_split_improvement * fmax(base_term, 1e-12);
+  }
+  return do_split;
+}
+
+// node i of the level: tree record, partition entry and (split nodes) the
+// children's links; k_idx = rank of i among the level's splitting nodes
+__device__ __forceinline__ void lf_write_node(int i, const NodeSplit& s, bool do_split, int k_idx, int base,
+                                              int next_base, const SplitParams& p, int nbt, const LevelOut& lv,
+                                              bool writer = true, PartInfo* local = nullptr) {
+  // writer = false (level prologue, every workgroup but the consumer launch's
+  // block 0): the same decisions and numbering, no global side effect; `local`
+  // receives the node's partition record (LDS copy of the calling workgroup)
+  if (do_split && 2 * (k_idx + 1) > lv.max_next_nodes) do_split = false;  // capacity guard
+  const int gid = base + i;
+  const double v = writer ? clamp_bound(leaf_value(s.G, s.H, s.W, p), p, gid, lv.tree_capacity) : 0.0;
+  const uint32_t* cat_src = nullptr;
+  PartInfo pi;
+  pi.gid = gid;
+  pi.leaf_children = 0;
+  pi.child_gid = -1;
+  pi.pad = 0;
+  TreeNode tn;
+  tn.value = (float)v;
+  tn.weight = (float)s.W;
+  tn.gain = do_split ? (float)s.gain : 0.0f;
+  if (do_split) {
+    pi.feat = s.feat; pi.bin = s.bin; pi.na_left = s.na_left; pi.child = 2 * k_idx;
+    tn.feat = s.feat; tn.bin = s.bin; tn.na_left = s.na_left; tn.left = next_base + 2 * k_idx;
+    if (writer) {
+      const int m = lv.nvb[s.feat];
+      tn.thr = (s.bin < m - 1) ? lv.edges[(int64_t)s.feat * nbt + s.bin] : INFINITY;
+    }
+    if (p.catf != nullptr && p.catf[s.feat] && gid < lv.tree_capacity) {
+      // categorical group split: the (node, feature) scan's left-set bitset
+      // becomes the tree's bitset of this node, and the partition record points at it
+      const uint32_t* src = p.fbcat + ((int64_t)i * p.F + s.feat) * 8;
+      uint32_t* dst = p.treecat + (int64_t)gid * 8;
+      if (writer) {
+#pragma unroll
+        for (int w = 0; w < 8; ++w) dst[w] = src[w];
+      }
+      cat_src = src;
+      part_set_cat(pi, dst, s.na_left);
+      tn.na_left = (s.na_left & 1) | 2;
+      tn.thr = __int_as_float(0x7fc00000);   // NaN: not a threshold split
+    }
+    const bool build_left = s.WL <= (s.W - s.WL);
+    NodeLink L, R;
+    L.parent = R.parent = i;
+    L.pad = R.pad = 0;
+    L.slot = build_left ? k_idx : -1;
+    L.sib_slot = build_left ? -1 : k_idx;
+    R.slot = build_left ? -1 : k_idx;
+    R.sib_slot = build_left ? k_idx : -1;
+    if (lv.next_link && writer) {
+      lv.next_link[2 * k_idx] = L;
+      lv.next_link[2 * k_idx + 1] = R;
+    }
+    pi.pad = (L.slot & 0xFFFF) | (R.slot << 16);  // children's build slots (partition -> slot16)
+    pi.child_gid = next_base + 2 * k_idx;
+    const int cg = next_base + 2 * k_idx;
+    if (writer && p.gbound != nullptr && cg + 1 < lv.tree_capacity) {
+      // monotone constraints: children inherit this node's interval; a split on a
+      // constrained feature cuts it at the midpoint of the (clipped) child values
+      double lo = -INFINITY, hi = INFINITY;
+      if (gid > 0 && gid < lv.tree_capacity) { lo = p.gbound[2 * gid]; hi = p.gbound[2 * gid + 1]; }
+      double llo = lo, lhi = hi, rlo = lo, rhi = hi;
+      const int mf = (int)p.mono[s.feat];
+      if (mf != 0) {
+        const double wl = fmin(fmax(leaf_value(s.GL, s.HL, s.WL, p), lo), hi);
+        const double wr = fmin(fmax(leaf_value(s.G - s.GL, s.H - s.HL, s.W - s.WL, p), lo), hi);
+        const double mid = 0.5 * (wl + wr);
+        if (mf > 0) { lhi = mid; rlo = mid; } else { llo = mid; rhi = mid; }
+      }
+      p.gbound[2 * cg] = llo; p.gbound[2 * cg + 1] = lhi;
+      p.gbound[2 * cg + 2] = rlo; p.gbound[2 * cg + 3] = rhi;
+    }
+    if (writer && p.istate != nullptr && cg + 1 < lv.tree_capacity && gid < lv.tree_capacity)
+      inter_children(p, gid, s.feat, cg);
+    if (p.children_leaves) pi.leaf_children = 1;
+    if (writer && p.children_leaves) {
+      // children are final: their totals come from this split's left stats
+      const double GR = s.G - s.GL, HR = s.H - s.HL, WR = s.W - s.WL;
+      TreeNode lc, rc;
+      lc.feat = rc.feat = -1;
+      lc.bin = rc.bin = 0;
+      lc.left = rc.left = -1;
+      lc.na_left = rc.na_left = 0;
+      lc.thr = rc.thr = 0.0f;
+      lc.gain = rc.gain = 0.0f;
+      lc.value = (float)clamp_bound(leaf_value(s.GL, s.HL, s.WL, p), p, cg, lv.tree_capacity);
+      rc.value = (float)clamp_bound(leaf_value(GR, HR, WR, p), p, cg + 1, lv.tree_capacity);
+      lc.weight = (float)s.WL;
+      rc.weight = (float)WR;
+      if (next_base + 2 * k_idx + 1 < lv.tree_capacity) {
+        lv.tree[next_base + 2 * k_idx] = lc;
+        lv.tree[next_base + 2 * k_idx + 1] = rc;
+      }
+    }
+  } else {
+    pi.feat = -1; pi.bin = 0; pi.na_left = 0; pi.child = -1;
+    tn.feat = -1; tn.bin = 0; tn.na_left = 0; tn.left = -1; tn.thr = 0.0f;
+  }
+  if (writer) {
+    lv.part[i] = pi;
+    if (gid < lv.tree_capacity) lv.tree[gid] = tn;
+  }
+  if (local) {
+    // the local copy of a categorical split tests the scan's bitset (written by
+    // an earlier launch, same bits) - never the tree's copy, which the writer
+    // workgroup stores during this launch
+    if (cat_src) part_set_cat(pi, cat_src, s.na_left);
+    *local = pi;
+  }
+}
+
+__device__ __forceinline__ void lf_write_ctl(int* __restrict__ ctl_next, int ks, int next_base, int max_next_nodes) {
+  if (2 * ks > max_next_nodes) ks = max_next_nodes / 2;
+  ctl_next[CTL_N] = 2 * ks;
+  ctl_next[CTL_SLOTS] = ks;
+  ctl_next[CTL_BASE] = next_base;
+  ctl_next[CTL_TOTAL] = next_base + 2 * ks;
+}
+
+// the level's records are in lv.nsplit (written before the caller's barrier)
+__device__ void level_finalize_body(const int* __restrict__ ctl, const SplitParams& p, int nbt, const LevelOut& lv) {
+  __shared__ int wsum[16];
+  __shared__ int carry;
+  const int n = ctl[CTL_N];
+  const int base = ctl[CTL_BASE];
+  const int next_base = base + n;
+  const int t = threadIdx.x, lane = t & 63, wid = t >> 6;
+  if (t == 0) carry = 0;
+  __syncthreads();
+  for (int c0 = 0; c0 < n; c0 += blockDim.x) {
+    const int i = c0 + t;
+    bool do_split = false;
+    NodeSplit s;
+    if (i < n) {
+      s = lv.nsplit[i];
+      do_split = lf_decide(s, p);
+    }
+    // block exclusive scan of do_split
+    const unsigned long long bal = __ballot(do_split);
+    const int within = __popcll(bal & ((1ull << lane) - 1ull));
+    if (lane == 0) wsum[wid] = __popcll(bal);
+    __syncthreads();
+    int before = carry;
+    for (int k = 0; k < wid; ++k) before += wsum[k];
+    if (i < n) lf_write_node(i, s, do_split, before + within, base, next_base, p, nbt, lv);
+    __syncthreads();
+    if (t == 0) {
+      int tot = 0;
+      for (int k = 0; k < (int)(blockDim.x >> 6); ++k) tot += wsum[k];
+      carry += tot;
+    }
+    __syncthreads();
+  }
+  if (t == 0) lf_write_ctl(lv.ctl_next, carry, next_base, lv.max_next_nodes);
+}
+
 // Level finalisation as the CONSUMER kernel's prologue (scan engine with fused
 // routing, one rank, levels of <= PRO_MAX_NODES nodes): instead of a
 // one-workgroup node_best_finalize launch between the level's split scan and
@@ -561,27 +845,90 @@ struct GradFuse {
 //    points at the scan's bitset (fbcat) instead of the tree's;
 //  * everything the prologue reads (fbest, the level's own ctl, the parents'
 //    gbound / istate, fbcat, edges, nvb) was written by earlier launches.
-struct FeatBest;
 constexpr int PRO_MAX_NODES = 64;
 struct LevelPro {
   const FeatBest* fbest;   // nullptr: no prologue (the level was finalised by its own launch)
-  int* ctl_next;
-  const float* edges;
-  const int* nvb;
-  PartInfo* part;
-  NodeLink* next_link;
-  TreeNode* tree;
-  NodeSplit* nsplit;
-  int max_next_nodes;
-  int tree_capacity;
+  LevelOut lv;
   SplitParams p;
 };
-// (defined after level_finalize_body) finalises the level of control block
-// `ctl`: ps_s[0 .. n) = its partition records, returns the next level's slot
-// count (= ctl_next[CTL_SLOTS]; its node count is twice that) to every thread.
-// ns_s: PRO_MAX_NODES records of LDS scratch, res_s: one LDS int.
+
+// The same finalisation as node_best_finalize_kernel for a level of
+// n <= PRO_MAX_NODES nodes, run by EVERY workgroup of the consumer launch (see
+// LevelPro for the rules): the waves take the nodes round-robin (records into
+// LDS), wave 0 decides and numbers the level in one ballot (one 64-node chunk
+// of level_finalize_body: carry = 0, no earlier wave).  writer: also store
+// the global results.  Called by all threads of the workgroup.
+// Finalises the level of control block `ctl`: ps_s[0 .. n) = its partition
+// records, returns the next level's slot count (= ctl_next[CTL_SLOTS]; its
+// node count is twice that) to every thread.  ns_s: PRO_MAX_NODES records of
+// LDS scratch, res_s: one LDS int.
 __device__ __forceinline__ int level_prologue(const LevelPro& lp, const int* __restrict__ ctl, int nbt, bool writer,
-                                              NodeSplit* ns_s, PartInfo* ps_s, int* res_s);
+                                              NodeSplit* ns_s, PartInfo* ps_s, int* res_s) {
+  const SplitParams& p = lp.p;
+  const LevelOut& lv = lp.lv;
+  const int n = min(ctl[CTL_N], PRO_MAX_NODES);   // the host sends only levels that fit
+  const int base = ctl[CTL_BASE];
+  const int next_base = base + n;
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, nw = blockDim.x >> 6;
+  // (loading every feature's whole record for several nodes in one round, the
+  // winner's fields by readlane, measured slower than this per-node chain:
+  // profiles/r7/fin_prologue_ab.txt)
+  for (int node = wid; node < n; node += nw) {
+    node_best_wave(lp.fbest, p.F, node, lane, ns_s);
+    if (writer && lane == 0) lv.nsplit[node] = ns_s[node];
+  }
+  __syncthreads();
+  if (wid == 0) {
+    const int i = lane;
+    bool do_split = false;
+    NodeSplit s;
+    if (i < n) {
+      s = ns_s[i];
+      do_split = lf_decide(s, p);
+    }
+    const unsigned long long bal = __ballot(do_split);
+    if (i < n)
+      lf_write_node(i, s, do_split, __popcll(bal & ((1ull << lane) - 1ull)), base, next_base, p, nbt, lv, writer,
+                    ps_s + i);
+    if (lane == 0) {
+      int ks = __popcll(bal);
+      if (writer) lf_write_ctl(lv.ctl_next, ks, next_base, lv.max_next_nodes);
+      if (2 * ks > lv.max_next_nodes) ks = lv.max_next_nodes / 2;   // as lf_write_ctl
+      *res_s = ks;
+    }
+  }
+  __syncthreads();
+  return *res_s;
+}
+
+// The level finalisation folded into the LAST workgroup of a level's reduce +
+// split-scan launch (one launch and one kernel boundary less per level): every
+// split record is stored write-through (agent scope, `sc1`), every wave drains
+// its stores before the workgroup's ticket (agent-scope atomic), and the
+// workgroup whose ticket comes last reads the records with `sc1` loads and runs
+// node_best + level_finalize_body - no release / acquire fences (round 5's
+// fenced version cost more than the launch it saved,
+// profiles/r5/fused_finalize_ab.txt).
+struct LevelFin {
+  LevelOut lv;
+  int* ticket;          // zeroed once; the last workgroup resets it
+};
+
+// Per-node arg-max and level finalisation by ONE workgroup (the 16 waves take
+// the nodes round-robin, then the workgroup finalises).  The NodeSplit records
+// go through global memory; the workgroup barrier (workgroup-scope fence +
+// s_barrier) orders them for the finalising threads.  MODE 0: records of an
+// earlier launch; 1: written by this launch's workgroups (agent-scope loads);
+// 2: pushed by peer ranks (system-scope loads)
+template <int MODE>
+__device__ void level_fin_records(const FeatBest* __restrict__ fbest, const int* __restrict__ ctl, const SplitParams& p,
+                                  int nbt, const LevelOut& lv) {
+  const int n = ctl[CTL_N];
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, nw = blockDim.x >> 6;
+  for (int node = wid; node < n; node += nw) node_best_wave<MODE>(fbest, p.F, node, lane, lv.nsplit);
+  __syncthreads();
+  level_finalize_body(ctl, p, nbt, lv);
+}
 
 constexpr int CMP_STAGE_BYTES = 2048;   // per wave
 constexpr int HB_PF = 1;     // feature code loads kept in flight per lane
@@ -1126,23 +1473,6 @@ __global__ __launch_bounds__(256) void hist_reduce_kernel(const unsigned long lo
 // owns bin t; grid = max_nodes x F so even a 16-node level fills the chip).
 // The per-node arg-max over features happens in level_finalize.
 // ---------------------------------------------------------------------------
-struct FeatBest {  // 64 B
-  double gain;
-  double GL, SL;   // left-child totals of the chosen threshold
-  double G, S;     // node totals (as seen from this feature's histogram)
-  double pad0;
-  int code;        // (bin * 2 + na_left), INT_MAX = none
-  int pad1;
-  double pad2;
-};
-
-// Best threshold of (node, f) computed by one wave; every lane returns the
-// same result (gain -inf / code INT_MAX = none).  Also stores the completed
-// histogram row into `full` (parent of the next level) when given.
-struct WaveBest {
-  double gain, GL, SL, G, S;
-  int code;
-};
 
 // Categorical (node, feature): H2O / LightGBM group split.  The non-empty
 // level bins are ordered by G / S (S = W or H by mode; ties by level code,
@@ -1547,14 +1877,6 @@ __device__ __forceinline__ WaveBest feat_best_wave(const long long* __restrict__
   return feat_scan_wave<NBT, CAT>(gi, si, allowed, node, f, nvb, ig, is, p);
 }
 
-__device__ __forceinline__ void store_feat_best(FeatBest* __restrict__ out, int64_t i, const WaveBest& w) {
-  FeatBest r{};
-  r.gain = w.gain; r.GL = w.GL; r.SL = w.SL;
-  r.G = w.G; r.S = w.S;
-  r.code = w.code;
-  out[i] = r;
-}
-
 // K3 tail + K5 fused: one 1024-thread workgroup per (built slot, feature)
 // sums that histogram row's workgroup slabs (16-byte loads: LANES slab lanes
 // x NBT / 2 bin pairs, 8 loads of a lane in flight), keeps the exact int64
@@ -1662,37 +1984,6 @@ __device__ __forceinline__ bool rs_scan_node(const long long (*row)[NBT], int sl
   return true;
 }
 
-// The level finalisation folded into the LAST workgroup of a level's reduce +
-// split-scan launch (one launch and one kernel boundary less per level): every
-// split record is stored write-through (agent scope, `sc1`), every wave drains
-// its stores before the workgroup's ticket (agent-scope atomic), and the
-// workgroup whose ticket comes last reads the records with `sc1` loads and runs
-// node_best + level_finalize_body - no release / acquire fences (round 5's
-// fenced version cost more than the launch it saved,
-// profiles/r5/fused_finalize_ab.txt).
-struct LevelFin {
-  int* ctl_next;
-  const float* edges;
-  PartInfo* part;
-  NodeLink* next_link;
-  TreeNode* tree;
-  NodeSplit* nsplit;
-  int* ticket;          // zeroed once; the last workgroup resets it
-  int max_next_nodes;
-  int tree_capacity;
-};
-
-__device__ __forceinline__ void store_feat_best_wt(FeatBest* __restrict__ out, int64_t i, const WaveBest& w) {
-  FeatBest* d = out + i;
-  __hip_atomic_store(&d->gain, w.gain, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  __hip_atomic_store(&d->GL, w.GL, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  __hip_atomic_store(&d->SL, w.SL, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  __hip_atomic_store(&d->G, w.G, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  __hip_atomic_store(&d->S, w.S, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  __hip_atomic_store(reinterpret_cast<long long*>(&d->code), (long long)(uint32_t)w.code, __ATOMIC_RELAXED,
-                     __HIP_MEMORY_SCOPE_AGENT);
-}
-
 // true (to every thread) in the workgroup whose ticket came last; every wave
 // has drained its stores before the ticket
 __device__ __forceinline__ bool lf_last_block(int* ticket, int nblocks) {
@@ -1708,12 +1999,7 @@ __device__ __forceinline__ bool lf_last_block(int* ticket, int nblocks) {
   return s_last != 0;
 }
 
-// (defined after level_finalize_body) MODE 1: records written by this launch's
-// workgroups (agent-scope loads); 2: pushed by peer ranks (system-scope loads)
-template <int MODE>
-__device__ void level_fin_records(const FeatBest* __restrict__ fbest, const int* __restrict__ ctl, const SplitParams& p,
-                                  const int* __restrict__ nvb, int nbt, const LevelFin& fin);
-
+// FIN: the launch's last workgroup finalises the level (LevelFin)
 template <int NBT, bool CAT, bool FIN = false>
 __global__ __launch_bounds__(1024) void reduce_split_kernel(
     const unsigned long long* __restrict__ partials, int wgpg, int fg, int slot_lo, int slot_cnt,
@@ -1737,7 +2023,7 @@ __global__ __launch_bounds__(1024) void reduce_split_kernel(
     }
   }
   if constexpr (FIN) {
-    if (lf_last_block(fin.ticket, (int)(gridDim.x * gridDim.y))) level_fin_records<1>(out, ctl, p, nvb, NBT, fin);
+    if (lf_last_block(fin.ticket, (int)(gridDim.x * gridDim.y))) level_fin_records<1>(out, ctl, p, NBT, fin.lv);
   }
 }
 
@@ -1797,7 +2083,7 @@ __global__ __launch_bounds__(1024) void reduce_split_p2p_kernel(
     p2pdev::P2PDesc d, const unsigned long long* __restrict__ partials, int wgpg, int fg, int slot_cnt,
     const long long* __restrict__ parent_full, long long* __restrict__ full, const int* __restrict__ ctl,
     const NodeLink* __restrict__ link, const int* __restrict__ nvb, const uint8_t* __restrict__ tree_fmask,
-    const double* __restrict__ qscale, SplitParams p, LevelFin fin) {
+    const double* __restrict__ qscale, SplitParams p, LevelOut lv) {
   __shared__ long long red[1024 / (NBT / 2)][NBT / 2][4];
   __shared__ long long row[2][NBT];
   __shared__ uint32_t s_epoch;
@@ -1870,7 +2156,7 @@ __global__ __launch_bounds__(1024) void reduce_split_p2p_kernel(
     if (last) {
       if (threadIdx.x < kWave) p2pdev::wave_wait(d, d.flags[d.rank] + p2pdev::kDoneBase, e);
       __syncthreads();
-      level_fin_records<2>(p2p_fbest_table(d, d.rank, e), ctl, p, nvb, NBT, fin);
+      level_fin_records<2>(p2p_fbest_table(d, d.rank, e), ctl, p, NBT, lv);
     }
   }
 }
@@ -1908,59 +2194,6 @@ __global__ __launch_bounds__(256) void split_find_kernel(const long long* __rest
   }
 }
 
-// Per-node arg-max over the features' best thresholds (gain desc, then
-// feature / bin / NA-direction asc): one wave per node, lane = feature.
-// MODE 0: plain loads (records of an earlier launch); 1: written by other
-// workgroups of this launch (agent-scope `sc1` loads); 2: pushed by peer ranks
-// (N-rank split table, system-scope loads; p2p_device.h)
-template <int MODE>
-__device__ __forceinline__ double fb_ld(const double* p) {
-  if constexpr (MODE == 2) return p2pdev::ld_sys(p);
-  else if constexpr (MODE == 1) return __hip_atomic_load(const_cast<double*>(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  else return *p;
-}
-template <int MODE>
-__device__ __forceinline__ int fb_code(const FeatBest* r) {
-  const uint32_t* c = reinterpret_cast<const uint32_t*>(&r->code);
-  if constexpr (MODE == 2) return (int)p2pdev::ld_sys(c);
-  else if constexpr (MODE == 1) return (int)__hip_atomic_load(const_cast<uint32_t*>(c), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  else return r->code;
-}
-
-template <int SYS = 0>
-__device__ __forceinline__ void node_best_wave(const FeatBest* __restrict__ fbest, int F, int node, int lane,
-                                               NodeSplit* __restrict__ out) {
-  const FeatBest* fb = fbest + (int64_t)node * F;
-  double bg = -INFINITY;
-  long long key = 0x7fffffffffffffffLL;  // (feature, code) order for ties
-  int bf = -1;
-  for (int f = lane; f < F; f += 64) {
-    const double gn = fb_ld<SYS>(&fb[f].gain);
-    const int code = fb_code<SYS>(&fb[f]);
-    if (code == 0x7fffffff || !(gn > -INFINITY)) continue;
-    const long long k = ((long long)f << 32) | (unsigned)code;
-    if (bf < 0 || gn > bg || (gn == bg && k < key)) { bg = gn; key = k; bf = f; }
-  }
-  wave_argmax_key(bg, key);
-  if (lane == 0) {
-    NodeSplit s;
-    // S is W (mode 0) or H (mode 1); exact leaf (G, H, W) sums come from the
-    // partition kernels, these only steer the split decisions
-    s.G = fb_ld<SYS>(&fb[0].G); s.H = fb_ld<SYS>(&fb[0].S); s.W = s.H;
-    s.pad = 0;
-    if (key != 0x7fffffffffffffffLL) {
-      const int f = (int)(key >> 32), code = (int)(key & 0xffffffff);
-      const FeatBest& c = fb[f];
-      s.gain = fb_ld<SYS>(&c.gain); s.GL = fb_ld<SYS>(&c.GL); s.HL = fb_ld<SYS>(&c.SL); s.WL = s.HL;
-      s.feat = f; s.bin = code >> 1; s.na_left = code & 1;
-    } else {
-      s.gain = -INFINITY; s.GL = s.HL = s.WL = 0.0;
-      s.feat = -1; s.bin = 0; s.na_left = 0;
-    }
-    out[node] = s;
-  }
-}
-
 __global__ __launch_bounds__(64) void node_best_kernel(const FeatBest* __restrict__ fbest,
                                                        const int* __restrict__ ctl, int F,
                                                        NodeSplit* __restrict__ out) {
@@ -1969,194 +2202,13 @@ __global__ __launch_bounds__(64) void node_best_kernel(const FeatBest* __restric
   node_best_wave(fbest, F, node, threadIdx.x, out);
 }
 
-// ---------------------------------------------------------------------------
-// Level finalisation (single workgroup): decide split/leaf per node, number
-// the children, pick the smaller child to build, write tree records and the
-// partition table.  ctl_next receives the next level's counts.
-// ---------------------------------------------------------------------------
-__device__ __forceinline__ bool lf_decide(const NodeSplit& s, const SplitParams& p) {
-  bool do_split = !p.is_last_level && s.feat >= 0 && isfinite(s.gain) && s.gain > 0.0;
-  if (do_split && p.mode == 0 && p.min_split_improvement > 0.0) {
-    // relative improvement over the node's explained sum of squares
-    const double base_term = (s.W > 0.0) ? s.G * s.G / s.W : 0.0;
-    do_split = s.gain > p.min_split_improvement * fmax(base_term, 1e-12);
-  }
-  return do_split;
-}
-
-// node i of the level: tree record, partition entry and (split nodes) the
-// children's links; k_idx = rank of i among the level's splitting nodes
-__device__ __forceinline__ void lf_write_node(int i, const NodeSplit& s, bool do_split, int k_idx, int base,
-                                              int next_base, int max_next_nodes, const SplitParams& p,
-                                              const float* __restrict__ edges, const int* __restrict__ nvb, int nbt,
-                                              PartInfo* __restrict__ part, NodeLink* __restrict__ next_link,
-                                              TreeNode* __restrict__ tree, int tree_capacity, bool writer = true,
-                                              PartInfo* local = nullptr) {
-  // writer = false (level prologue, every workgroup but the consumer launch's
-  // block 0): the same decisions and numbering, no global side effect; `local`
-  // receives the node's partition record (LDS copy of the calling workgroup)
-  if (do_split && 2 * (k_idx + 1) > max_next_nodes) do_split = false;  // capacity guard
-  const int gid = base + i;
-  const double v = writer ? clamp_bound(leaf_value(s.G, s.H, s.W, p), p, gid, tree_capacity) : 0.0;
-  const uint32_t* cat_src = nullptr;
-  PartInfo pi;
-  pi.gid = gid;
-  pi.leaf_children = 0;
-  pi.child_gid = -1;
-  pi.pad = 0;
-  TreeNode tn;
-  tn.value = (float)v;
-  tn.weight = (float)s.W;
-  tn.gain = do_split ? (float)s.gain : 0.0f;
-  if (do_split) {
-    pi.feat = s.feat; pi.bin = s.bin; pi.na_left = s.na_left; pi.child = 2 * k_idx;
-    tn.feat = s.feat; tn.bin = s.bin; tn.na_left = s.na_left; tn.left = next_base + 2 * k_idx;
-    if (writer) {
-      const int m = nvb[s.feat];
-      tn.thr = (s.bin < m - 1) ? edges[(int64_t)s.feat * nbt + s.bin] : INFINITY;
-    }
-    if (p.catf != nullptr && p.catf[s.feat] && gid < tree_capacity) {
-      // categorical group split: the (node, feature) scan's left-set bitset
-      // becomes the tree's bitset of this node, and the partition record points at it
-      const uint32_t* src = p.fbcat + ((int64_t)i * p.F + s.feat) * 8;
-      uint32_t* dst = p.treecat + (int64_t)gid * 8;
-      if (writer) {
-#pragma unroll
-        for (int w = 0; w < 8; ++w) dst[w] = src[w];
-      }
-      cat_src = src;
-      part_set_cat(pi, dst, s.na_left);
-      tn.na_left = (s.na_left & 1) | 2;
-      tn.thr = __int_as_float(0x7fc00000);   // NaN: not a threshold split
-    }
-    const bool build_left = s.WL <= (s.W - s.WL);
-    NodeLink L, R;
-    L.parent = R.parent = i;
-    L.pad = R.pad = 0;
-    L.slot = build_left ? k_idx : -1;
-    L.sib_slot = build_left ? -1 : k_idx;
-    R.slot = build_left ? -1 : k_idx;
-    R.sib_slot = build_left ? k_idx : -1;
-    if (next_link && writer) {
-      next_link[2 * k_idx] = L;
-      next_link[2 * k_idx + 1] = R;
-    }
-    pi.pad = (L.slot & 0xFFFF) | (R.slot << 16);  // children's build slots (partition -> slot16)
-    pi.child_gid = next_base + 2 * k_idx;
-    const int cg = next_base + 2 * k_idx;
-    if (writer && p.gbound != nullptr && cg + 1 < tree_capacity) {
-      // monotone constraints: children inherit this node's interval; a split on a
-      // constrained feature cuts it at the midpoint of the (clipped) child values
-      double lo = -INFINITY, hi = INFINITY;
-      if (gid > 0 && gid < tree_capacity) { lo = p.gbound[2 * gid]; hi = p.gbound[2 * gid + 1]; }
-      double llo = lo, lhi = hi, rlo = lo, rhi = hi;
-      const int mf = (int)p.mono[s.feat];
-      if (mf != 0) {
-        const double wl = fmin(fmax(leaf_value(s.GL, s.HL, s.WL, p), lo), hi);
-        const double wr = fmin(fmax(leaf_value(s.G - s.GL, s.H - s.HL, s.W - s.WL, p), lo), hi);
-        const double mid = 0.5 * (wl + wr);
-        if (mf > 0) { lhi = mid; rlo = mid; } else { llo = mid; rhi = mid; }
-      }
-      p.gbound[2 * cg] = llo; p.gbound[2 * cg + 1] = lhi;
-      p.gbound[2 * cg + 2] = rlo; p.gbound[2 * cg + 3] = rhi;
-    }
-    if (writer && p.istate != nullptr && cg + 1 < tree_capacity && gid < tree_capacity)
-      inter_children(p, gid, s.feat, cg);
-    if (p.children_leaves) pi.leaf_children = 1;
-    if (writer && p.children_leaves) {
-      // children are final: their totals come from this split's left stats
-      const double GR = s.G - s.GL, HR = s.H - s.HL, WR = s.W - s.WL;
-      TreeNode lc, rc;
-      lc.feat = rc.feat = -1;
-      lc.bin = rc.bin = 0;
-      lc.left = rc.left = -1;
-      lc.na_left = rc.na_left = 0;
-      lc.thr = rc.thr = 0.0f;
-      lc.gain = rc.gain = 0.0f;
-      lc.value = (float)clamp_bound(leaf_value(s.GL, s.HL, s.WL, p), p, cg, tree_capacity);
-      rc.value = (float)clamp_bound(leaf_value(GR, HR, WR, p), p, cg + 1, tree_capacity);
-      lc.weight = (float)s.WL;
-      rc.weight = (float)WR;
-      if (next_base + 2 * k_idx + 1 < tree_capacity) {
-        tree[next_base + 2 * k_idx] = lc;
-        tree[next_base + 2 * k_idx + 1] = rc;
-      }
-    }
-  } else {
-    pi.feat = -1; pi.bin = 0; pi.na_left = 0; pi.child = -1;
-    tn.feat = -1; tn.bin = 0; tn.na_left = 0; tn.left = -1; tn.thr = 0.0f;
-  }
-  if (writer) {
-    part[i] = pi;
-    if (gid < tree_capacity) tree[gid] = tn;
-  }
-  if (local) {
-    // the local copy of a categorical split tests the scan's bitset (written by
-    // an earlier launch, same bits) - never the tree's copy, which the writer
-    // workgroup stores during this launch
-    if (cat_src) part_set_cat(pi, cat_src, s.na_left);
-    *local = pi;
-  }
-}
-
-__device__ __forceinline__ void lf_write_ctl(int* __restrict__ ctl_next, int ks, int next_base, int max_next_nodes) {
-  if (2 * ks > max_next_nodes) ks = max_next_nodes / 2;
-  ctl_next[CTL_N] = 2 * ks;
-  ctl_next[CTL_SLOTS] = ks;
-  ctl_next[CTL_BASE] = next_base;
-  ctl_next[CTL_TOTAL] = next_base + 2 * ks;
-}
-
-__device__ void level_finalize_body(const NodeSplit* __restrict__ nsplit, const int* __restrict__ ctl,
-                                    int* __restrict__ ctl_next, const SplitParams& p, const float* __restrict__ edges,
-                                    const int* __restrict__ nvb, int nbt, int max_next_nodes,
-                                    PartInfo* __restrict__ part, NodeLink* __restrict__ next_link,
-                                    TreeNode* __restrict__ tree, int tree_capacity) {
-  __shared__ int wsum[16];
-  __shared__ int carry;
-  const int n = ctl[CTL_N];
-  const int base = ctl[CTL_BASE];
-  const int next_base = base + n;
-  const int t = threadIdx.x, lane = t & 63, wid = t >> 6;
-  if (t == 0) carry = 0;
-  __syncthreads();
-  for (int c0 = 0; c0 < n; c0 += blockDim.x) {
-    const int i = c0 + t;
-    bool do_split = false;
-    NodeSplit s;
-    if (i < n) {
-      s = nsplit[i];
-      do_split = lf_decide(s, p);
-    }
-    // block exclusive scan of do_split
-    const unsigned long long bal = __ballot(do_split);
-    const int within = __popcll(bal & ((1ull << lane) - 1ull));
-    if (lane == 0) wsum[wid] = __popcll(bal);
-    __syncthreads();
-    int before = carry;
-    for (int k = 0; k < wid; ++k) before += wsum[k];
-    if (i < n)
-      lf_write_node(i, s, do_split, before + within, base, next_base, max_next_nodes, p, edges, nvb, nbt, part,
-                    next_link, tree, tree_capacity);
-    __syncthreads();
-    if (t == 0) {
-      int tot = 0;
-      for (int k = 0; k < (int)(blockDim.x >> 6); ++k) tot += wsum[k];
-      carry += tot;
-    }
-    __syncthreads();
-  }
-  if (t == 0) lf_write_ctl(ctl_next, carry, next_base, max_next_nodes);
-}
-
 // Multi-block level finalisation (levels with tens of thousands of nodes,
 // where one workgroup walking the level took ~0.9 ms at depth 19): count the
 // splitting nodes per 1024-node tile, scan the tile counts in one small
 // workgroup, then every tile numbers its nodes from its prefix.  Same
 // decisions and numbering as level_finalize_body.
 constexpr int LF_TILE = 1024;
-__global__ __launch_bounds__(LF_TILE) void lf_count_kernel(const NodeSplit* __restrict__ nsplit,
-                                                           const int* __restrict__ ctl, SplitParams p,
+__global__ __launch_bounds__(LF_TILE) void lf_count_kernel(const int* __restrict__ ctl, SplitParams p, LevelOut lv,
                                                            int* __restrict__ tiles) {
   __shared__ int wsum[16];
   const int n = ctl[CTL_N];
@@ -2166,7 +2218,7 @@ __global__ __launch_bounds__(LF_TILE) void lf_count_kernel(const NodeSplit* __re
     if (t == 0) tiles[blockIdx.x] = 0;
     return;
   }
-  const bool do_split = i < n && lf_decide(nsplit[i], p);
+  const bool do_split = i < n && lf_decide(lv.nsplit[i], p);
   const unsigned long long bal = __ballot(do_split);
   if (lane == 0) wsum[wid] = __popcll(bal);
   __syncthreads();
@@ -2178,7 +2230,7 @@ __global__ __launch_bounds__(LF_TILE) void lf_count_kernel(const NodeSplit* __re
 }
 
 __global__ __launch_bounds__(1024) void lf_scan_kernel(int* __restrict__ tiles, int ntiles, const int* __restrict__ ctl,
-                                                       int* __restrict__ ctl_next, int max_next_nodes) {
+                                                       LevelOut lv) {
   __shared__ int wsum[16];
   __shared__ int carry;
   const int t = threadIdx.x, lane = t & 63, wid = t >> 6;
@@ -2206,17 +2258,11 @@ __global__ __launch_bounds__(1024) void lf_scan_kernel(int* __restrict__ tiles, 
     }
     __syncthreads();
   }
-  if (t == 0) lf_write_ctl(ctl_next, carry, ctl[CTL_BASE] + ctl[CTL_N], max_next_nodes);
+  if (t == 0) lf_write_ctl(lv.ctl_next, carry, ctl[CTL_BASE] + ctl[CTL_N], lv.max_next_nodes);
 }
 
-__global__ __launch_bounds__(LF_TILE) void lf_write_kernel(const NodeSplit* __restrict__ nsplit,
-                                                           const int* __restrict__ ctl, SplitParams p,
-                                                           const float* __restrict__ edges,
-                                                           const int* __restrict__ nvb, int nbt, int max_next_nodes,
-                                                           PartInfo* __restrict__ part,
-                                                           NodeLink* __restrict__ next_link,
-                                                           TreeNode* __restrict__ tree, int tree_capacity,
-                                                           const int* __restrict__ tiles) {
+__global__ __launch_bounds__(LF_TILE) void lf_write_kernel(const int* __restrict__ ctl, SplitParams p, int nbt,
+                                                           LevelOut lv, const int* __restrict__ tiles) {
   __shared__ int wsum[16];
   const int n = ctl[CTL_N];
   if (blockIdx.x * LF_TILE >= n) return;
@@ -2226,7 +2272,7 @@ __global__ __launch_bounds__(LF_TILE) void lf_write_kernel(const NodeSplit* __re
   NodeSplit s;
   bool do_split = false;
   if (i < n) {
-    s = nsplit[i];
+    s = lv.nsplit[i];
     do_split = lf_decide(s, p);
   }
   const unsigned long long bal = __ballot(do_split);
@@ -2235,100 +2281,32 @@ __global__ __launch_bounds__(LF_TILE) void lf_write_kernel(const NodeSplit* __re
   int before = tiles[blockIdx.x];
   for (int k = 0; k < wid; ++k) before += wsum[k];
   if (i < n)
-    lf_write_node(i, s, do_split, before + __popcll(bal & ((1ull << lane) - 1ull)), base, base + n, max_next_nodes,
-                  p, edges, nvb, nbt, part, next_link, tree, tree_capacity);
+    lf_write_node(i, s, do_split, before + __popcll(bal & ((1ull << lane) - 1ull)), base, base + n, p, nbt, lv);
 }
 
-__global__ __launch_bounds__(1024) void level_finalize_kernel(const NodeSplit* __restrict__ nsplit,
-                                                              const int* __restrict__ ctl, int* __restrict__ ctl_next,
-                                                              SplitParams p, const float* __restrict__ edges,
-                                                              const int* __restrict__ nvb, int nbt,
-                                                              int max_next_nodes, PartInfo* __restrict__ part,
-                                                              NodeLink* __restrict__ next_link,
-                                                              TreeNode* __restrict__ tree, int tree_capacity) {
-  level_finalize_body(nsplit, ctl, ctl_next, p, edges, nvb, nbt, max_next_nodes, part, next_link, tree,
-                      tree_capacity);
+// the level's records are already in lv.nsplit
+__global__ __launch_bounds__(1024) void level_finalize_kernel(const int* __restrict__ ctl, SplitParams p, int nbt,
+                                                              LevelOut lv) {
+  level_finalize_body(ctl, p, nbt, lv);
 }
 
-// Per-node arg-max and level finalisation in ONE single-workgroup launch (the
-// 16 waves take the nodes round-robin, then the workgroup finalises): saves a
-// dependent launch per level on the scan engine, whose levels hold few nodes.
-// The NodeSplit records go through global memory; the workgroup barrier
-// (workgroup-scope fence + s_barrier) orders them for the finalising threads.
-__global__ __launch_bounds__(1024) void node_best_finalize_kernel(
-    const FeatBest* __restrict__ fbest, const int* __restrict__ ctl, int* __restrict__ ctl_next, SplitParams p,
-    const float* __restrict__ edges, const int* __restrict__ nvb, int nbt, int max_next_nodes,
-    PartInfo* __restrict__ part, NodeLink* __restrict__ next_link, TreeNode* __restrict__ tree, int tree_capacity,
-    NodeSplit* __restrict__ nsplit) {
-  const int n = ctl[CTL_N];
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, nw = blockDim.x >> 6;
-  for (int node = wid; node < n; node += nw) node_best_wave(fbest, p.F, node, lane, nsplit);
-  __syncthreads();
-  level_finalize_body(nsplit, ctl, ctl_next, p, edges, nvb, nbt, max_next_nodes, part, next_link, tree,
-                      tree_capacity);
-}
-
-// The same finalisation as node_best_finalize_kernel for a level of
-// n <= PRO_MAX_NODES nodes, run by EVERY workgroup of the consumer launch (see
-// LevelPro for the rules): the waves take the nodes round-robin (records into
-// LDS), wave 0 decides and numbers the level in one ballot (one 64-node chunk
-// of level_finalize_body: carry = 0, no earlier wave).  writer: also store
-// the global results.  Called by all threads of the workgroup.
-__device__ __forceinline__ int level_prologue(const LevelPro& lp, const int* __restrict__ ctl, int nbt, bool writer,
-                                              NodeSplit* ns_s, PartInfo* ps_s, int* res_s) {
-  const SplitParams& p = lp.p;
-  const int n = min(ctl[CTL_N], PRO_MAX_NODES);   // the host sends only levels that fit
-  const int base = ctl[CTL_BASE];
-  const int next_base = base + n;
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, nw = blockDim.x >> 6;
-  // (loading every feature's whole record for several nodes in one round, the
-  // winner's fields by readlane, measured slower than this per-node chain:
-  // profiles/r7/fin_prologue_ab.txt)
-  for (int node = wid; node < n; node += nw) {
-    node_best_wave(lp.fbest, p.F, node, lane, ns_s);
-    if (writer && lane == 0) lp.nsplit[node] = ns_s[node];
-  }
-  __syncthreads();
-  if (wid == 0) {
-    const int i = lane;
-    bool do_split = false;
-    NodeSplit s;
-    if (i < n) {
-      s = ns_s[i];
-      do_split = lf_decide(s, p);
-    }
-    const unsigned long long bal = __ballot(do_split);
-    if (i < n)
-      lf_write_node(i, s, do_split, __popcll(bal & ((1ull << lane) - 1ull)), base, next_base, lp.max_next_nodes, p,
-                    lp.edges, lp.nvb, nbt, lp.part, lp.next_link, lp.tree, lp.tree_capacity, writer, ps_s + i);
-    if (lane == 0) {
-      int ks = __popcll(bal);
-      if (writer) lf_write_ctl(lp.ctl_next, ks, next_base, lp.max_next_nodes);
-      if (2 * ks > lp.max_next_nodes) ks = lp.max_next_nodes / 2;   // as lf_write_ctl
-      *res_s = ks;
-    }
-  }
-  __syncthreads();
-  return *res_s;
+// Per-node arg-max and level finalisation in ONE single-workgroup launch
+// (level_fin_records): saves a dependent launch per level on the scan engine,
+// whose levels hold few nodes.
+__global__ __launch_bounds__(1024) void node_best_finalize_kernel(const FeatBest* __restrict__ fbest,
+                                                                  const int* __restrict__ ctl, SplitParams p,
+                                                                  int nbt, LevelOut lv) {
+  level_fin_records<0>(fbest, ctl, p, nbt, lv);
 }
 
 // N ranks (after reduce_split_p2p): wait for every rank's done word, then the
 // same per-node arg-max over the all-gathered split table + finalisation.
 // Identical records on every rank -> identical trees.
-__global__ __launch_bounds__(1024) void node_best_finalize_p2p_kernel(
-    p2pdev::P2PDesc d, const int* __restrict__ ctl, int* __restrict__ ctl_next, SplitParams p,
-    const float* __restrict__ edges, const int* __restrict__ nvb, int nbt, int max_next_nodes,
-    PartInfo* __restrict__ part, NodeLink* __restrict__ next_link, TreeNode* __restrict__ tree, int tree_capacity,
-    NodeSplit* __restrict__ nsplit) {
+__global__ __launch_bounds__(1024) void node_best_finalize_p2p_kernel(p2pdev::P2PDesc d, const int* __restrict__ ctl,
+                                                                      SplitParams p, int nbt, LevelOut lv) {
   __shared__ uint32_t s_epoch;
   const uint32_t e = p2pdev::wait_done(d, &s_epoch);
-  const FeatBest* fbest = p2p_fbest_table(d, d.rank, e);
-  const int n = ctl[CTL_N];
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, nw = blockDim.x >> 6;
-  for (int node = wid; node < n; node += nw) node_best_wave<2>(fbest, p.F, node, lane, nsplit);
-  __syncthreads();
-  level_finalize_body(nsplit, ctl, ctl_next, p, edges, nvb, nbt, max_next_nodes, part, next_link, tree,
-                      tree_capacity);
+  level_fin_records<2>(p2p_fbest_table(d, d.rank, e), ctl, p, nbt, lv);
 }
 
 
@@ -3193,6 +3171,8 @@ H2OMX_API int h2omx_tree_sizes(int* out) {
   out[3] = sizeof(PartInfo);
   out[4] = sizeof(TreeNode);
   out[5] = sizeof(GradParams);
+  out[6] = sizeof(LevelOut);
+  out[7] = sizeof(NodeSplit);
   return kOk;
 }
 
@@ -3204,21 +3184,23 @@ H2OMX_API int h2omx_bin_features(const float* X, int64_t ld, int64_t n, int F, c
   return launch_status();
 }
 
+// `level_out` of the entry points below: the caller's LevelOut image, copied
+// like `params`.  False: a null record or a null required member (edges and
+// next_link may be null).
+static bool copy_level_out(LevelOut& lv, const void* level_out) {
+  if (level_out == nullptr) return false;
+  lv = *reinterpret_cast<const LevelOut*>(level_out);
+  return lv.ctl_next != nullptr && lv.nvb != nullptr && lv.part != nullptr && lv.tree != nullptr &&
+         lv.nsplit != nullptr;
+}
+
 // Level prologue arguments (LevelPro): the finalisation's inputs and outputs,
 // exactly those of h2omx_level_finalize for the same level.
-static bool make_pro(LevelPro& lp, const void* fbest, const void* params, int* ctl_next, const float* edges,
-                     const int* nvb, int max_next_nodes, void* part, void* next_link, void* tree, int tree_capacity,
-                     void* nsplit, int max_nodes) {
-  if (fbest == nullptr || params == nullptr || ctl_next == nullptr || nvb == nullptr || part == nullptr ||
-      tree == nullptr || nsplit == nullptr || max_nodes < 1 || max_nodes > PRO_MAX_NODES)
-    return false;
+static bool make_pro(LevelPro& lp, const void* fbest, const void* params, const void* level_out, int max_nodes) {
+  if (fbest == nullptr || params == nullptr || max_nodes < 1 || max_nodes > PRO_MAX_NODES) return false;
   lp.fbest = reinterpret_cast<const FeatBest*>(fbest);
-  lp.ctl_next = ctl_next; lp.edges = edges; lp.nvb = nvb; lp.part = reinterpret_cast<PartInfo*>(part);
-  lp.next_link = reinterpret_cast<NodeLink*>(next_link); lp.tree = reinterpret_cast<TreeNode*>(tree);
-  lp.nsplit = reinterpret_cast<NodeSplit*>(nsplit);
-  lp.max_next_nodes = max_next_nodes; lp.tree_capacity = tree_capacity;
   lp.p = *reinterpret_cast<const SplitParams*>(params);
-  return true;
+  return copy_level_out(lp.lv, level_out);
 }
 
 static int hist_build_launch(const uint8_t* codes, int64_t npad, const float* g, const float* s2, const int* nid,
@@ -3234,7 +3216,10 @@ static int hist_build_launch(const uint8_t* codes, int64_t npad, const float* g,
   // level prologue: the previous level is finalised inside this (routing, writer) launch
   LevelPro lpz{};
   if (lpp) lpz = *lpp;
-  if (lpp && (!route || !writer || lpz.fbest == nullptr || lpz.nsplit == nullptr)) return kBadArg;
+  // (ctl / part_prev are the prologue's own outputs: what block 0 writes)
+  if (lpp && (!route || !writer || lpz.fbest == nullptr || lpz.lv.nsplit == nullptr || lpz.lv.ctl_next != ctl ||
+              (const void*)lpz.lv.part != part_prev))
+    return kBadArg;
   // pkm bit 3: wave-compacted atomics (CMP; stored rows, 16-row units, <= 64 slots per pass)
   const bool cmp = (pkm & 8) != 0;
   // pkm bit 4 / 5: level-0 histograms in 8 / 4 interleaved lane copies (PKM 1 / 3 only)
@@ -3391,19 +3376,17 @@ H2OMX_API int h2omx_hist_build_route(const uint8_t* codes, int64_t npad, const i
 // h2omx_hist_build_route that also finalises the previous level (level
 // prologue, LevelPro) - replaces h2omx_level_finalize + h2omx_hist_build_route
 // for one-pass levels whose previous level holds <= 64 nodes.  ctl_prev is that
-// level's control block; `ctl` (its ctl_next), part_prev (its part), next_link,
-// tree and nsplit are written by block 0.
+// level's control block; level_out is that level's LevelOut: `ctl` (its
+// ctl_next), part_prev (its part), next_link, tree and nsplit are written by
+// block 0.
 H2OMX_API int h2omx_hist_build_route_fin(const uint8_t* codes, int64_t npad, const int* nid_prev, void* part_prev,
                                          const int* ctl_prev, int* nid_out, int* ctl, const int* nvb,
                                          const double* qscale, int F, int nbt, int fg, int n_groups, int wgpg,
                                          int slot_cnt, int rows_per_lane, int threads, unsigned long long* pk_buf,
                                          int pkm, unsigned long long* partials, const void* fbest, const void* params,
-                                         const float* edges, int max_next_nodes, void* next_link, void* tree,
-                                         int tree_capacity, void* nsplit, int max_nodes, hipStream_t stream) {
+                                         const void* level_out, int max_nodes, hipStream_t stream) {
   LevelPro lp{};
-  if (!make_pro(lp, fbest, params, ctl, edges, nvb, max_next_nodes, part_prev, next_link, tree, tree_capacity, nsplit,
-                max_nodes))
-    return kBadArg;
+  if (!make_pro(lp, fbest, params, level_out, max_nodes)) return kBadArg;
   return hist_build_launch(codes, npad, nullptr, nullptr, nid_prev, nullptr, ctl, nvb, qscale, 0, F, nbt, fg, n_groups,
                            wgpg, 0, slot_cnt, rows_per_lane, threads, nullptr, pk_buf, pkm, partials, part_prev,
                            ctl_prev, nid_out, 1, stream, nullptr, &lp);
@@ -3442,23 +3425,28 @@ H2OMX_API int h2omx_split_find(const long long* built, const long long* parent_f
   return launch_status();
 }
 
-H2OMX_API int h2omx_reduce_split(const unsigned long long* partials, int wgpg, int fg, int slot_lo, int slot_cnt,
-                                 const long long* parent_full, long long* full, const int* ctl, const void* link,
-                                 const int* nvb, const uint8_t* tree_fmask, const double* qscale, const void* params,
-                                 int nbt, void* out, hipStream_t stream) {
+// finp (h2omx_reduce_split_fin): the launch's last workgroup finalises the level
+static int reduce_split_launch(const unsigned long long* partials, int wgpg, int fg, int slot_lo, int slot_cnt,
+                               const long long* parent_full, long long* full, const int* ctl, const void* link,
+                               const int* nvb, const uint8_t* tree_fmask, const double* qscale, const void* params,
+                               int nbt, void* out, hipStream_t stream, const LevelFin* finp = nullptr) {
   const SplitParams p = *reinterpret_cast<const SplitParams*>(params);
   if (slot_cnt < 1 || wgpg < 1 || fg < 1 || p.F < 1) return kBadArg;
   const NodeLink* lk = reinterpret_cast<const NodeLink*>(link);
   FeatBest* o = reinterpret_cast<FeatBest*>(out);
   const dim3 grid(slot_cnt, p.F);
-  const LevelFin nofin{};
-#define LAUNCH_RS(NB)                                                                                              \
-  if (p.catf != nullptr)                                                                                          \
-    hipLaunchKernelGGL((reduce_split_kernel<NB, true>), grid, dim3(1024), 0, stream, partials, wgpg, fg, slot_lo, \
-                       slot_cnt, parent_full, full, ctl, lk, nvb, tree_fmask, qscale, p, o, nofin);               \
-  else                                                                                                            \
-    hipLaunchKernelGGL((reduce_split_kernel<NB, false>), grid, dim3(1024), 0, stream, partials, wgpg, fg,         \
-                       slot_lo, slot_cnt, parent_full, full, ctl, lk, nvb, tree_fmask, qscale, p, o, nofin)
+  LevelFin fin{};
+  if (finp) fin = *finp;
+#define LAUNCH_RSK(NB, CAT, FIN)                                                                                \
+  hipLaunchKernelGGL((reduce_split_kernel<NB, CAT, FIN>), grid, dim3(1024), 0, stream, partials, wgpg, fg, slot_lo, \
+                     slot_cnt, parent_full, full, ctl, lk, nvb, tree_fmask, qscale, p, o, fin)
+#define LAUNCH_RS(NB)                                           \
+  do {                                                          \
+    if (p.catf != nullptr && finp) LAUNCH_RSK(NB, true, true);  \
+    else if (p.catf != nullptr) LAUNCH_RSK(NB, true, false);    \
+    else if (finp) LAUNCH_RSK(NB, false, true);                 \
+    else LAUNCH_RSK(NB, false, false);                          \
+  } while (0)
   switch (nbt) {
     case 32: LAUNCH_RS(32); break;
     case 64: LAUNCH_RS(64); break;
@@ -3467,51 +3455,32 @@ H2OMX_API int h2omx_reduce_split(const unsigned long long* partials, int wgpg, i
     default: return kBadArg;
   }
 #undef LAUNCH_RS
+#undef LAUNCH_RSK
   return launch_status();
+}
+
+H2OMX_API int h2omx_reduce_split(const unsigned long long* partials, int wgpg, int fg, int slot_lo, int slot_cnt,
+                                 const long long* parent_full, long long* full, const int* ctl, const void* link,
+                                 const int* nvb, const uint8_t* tree_fmask, const double* qscale, const void* params,
+                                 int nbt, void* out, hipStream_t stream) {
+  return reduce_split_launch(partials, wgpg, fg, slot_lo, slot_cnt, parent_full, full, ctl, link, nvb, tree_fmask,
+                             qscale, params, nbt, out, stream);
 }
 
 // One-pass level (slot_lo = 0, slot_cnt = the level's slots) with the level
 // finalisation in its last workgroup (LevelFin): replaces reduce_split +
 // level_finalize (node_best_finalize) for levels of <= 64 nodes.  ticket: an
 // int zeroed once (each launch leaves it zero).
-static LevelFin make_fin(int* ctl_next, const float* edges, int max_next_nodes, void* part, void* next_link,
-                         void* tree, int tree_capacity, void* nsplit, int* ticket) {
-  LevelFin f;
-  f.ctl_next = ctl_next; f.edges = edges; f.part = reinterpret_cast<PartInfo*>(part);
-  f.next_link = reinterpret_cast<NodeLink*>(next_link); f.tree = reinterpret_cast<TreeNode*>(tree);
-  f.nsplit = reinterpret_cast<NodeSplit*>(nsplit); f.ticket = ticket;
-  f.max_next_nodes = max_next_nodes; f.tree_capacity = tree_capacity;
-  return f;
-}
-
 H2OMX_API int h2omx_reduce_split_fin(const unsigned long long* partials, int wgpg, int fg, int slot_cnt,
                                      const long long* parent_full, long long* full, const int* ctl, const void* link,
                                      const int* nvb, const uint8_t* tree_fmask, const double* qscale,
-                                     const void* params, int nbt, void* out, int* ctl_next, const float* edges,
-                                     int max_next_nodes, void* part, void* next_link, void* tree, int tree_capacity,
-                                     void* nsplit, int* ticket, hipStream_t stream) {
-  const SplitParams p = *reinterpret_cast<const SplitParams*>(params);
-  if (slot_cnt < 1 || wgpg < 1 || fg < 1 || p.F < 1 || ticket == nullptr || nsplit == nullptr) return kBadArg;
-  const NodeLink* lk = reinterpret_cast<const NodeLink*>(link);
-  FeatBest* o = reinterpret_cast<FeatBest*>(out);
-  const dim3 grid(slot_cnt, p.F);
-  const LevelFin fin = make_fin(ctl_next, edges, max_next_nodes, part, next_link, tree, tree_capacity, nsplit, ticket);
-#define LAUNCH_RSF(NB)                                                                                             \
-  if (p.catf != nullptr)                                                                                          \
-    hipLaunchKernelGGL((reduce_split_kernel<NB, true, true>), grid, dim3(1024), 0, stream, partials, wgpg, fg, 0,  \
-                       slot_cnt, parent_full, full, ctl, lk, nvb, tree_fmask, qscale, p, o, fin);                 \
-  else                                                                                                            \
-    hipLaunchKernelGGL((reduce_split_kernel<NB, false, true>), grid, dim3(1024), 0, stream, partials, wgpg, fg, 0, \
-                       slot_cnt, parent_full, full, ctl, lk, nvb, tree_fmask, qscale, p, o, fin)
-  switch (nbt) {
-    case 32: LAUNCH_RSF(32); break;
-    case 64: LAUNCH_RSF(64); break;
-    case 128: LAUNCH_RSF(128); break;
-    case 256: LAUNCH_RSF(256); break;
-    default: return kBadArg;
-  }
-#undef LAUNCH_RSF
-  return launch_status();
+                                     const void* params, int nbt, void* out, const void* level_out, int* ticket,
+                                     hipStream_t stream) {
+  LevelFin fin{};
+  if (!copy_level_out(fin.lv, level_out) || ticket == nullptr) return kBadArg;
+  fin.ticket = ticket;
+  return reduce_split_launch(partials, wgpg, fg, 0, slot_cnt, parent_full, full, ctl, link, nvb, tree_fmask, qscale,
+                             params, nbt, out, stream, &fin);
 }
 
 // N-rank fused level (reduce_split_p2p_kernel); desc = host P2PDesc image.
@@ -3519,17 +3488,15 @@ H2OMX_API int h2omx_reduce_split_fin(const unsigned long long* partials, int wgp
 // levels through hist_reduce + all-reduce + split_find.  The split records
 // land in the symmetric buffer's split table (h2omx_node_best_finalize_p2p
 // reads them); capacity: the pushed rows fit a parity, the records half of one.
-// With a ticket (non-null), the launch's last workgroup also waits for every
-// rank's done word and finalises the level (node_best_finalize_p2p folded in:
-// the ticket is unused beyond selecting that mode - the P2P finish ticket
-// picks the workgroup).
+// With a level_out (non-null), the launch's last workgroup also waits for
+// every rank's done word and finalises the level (node_best_finalize_p2p
+// folded in; the P2P finish ticket picks the workgroup).  Null: no
+// finalisation in this launch.
 H2OMX_API int h2omx_reduce_split_p2p(const void* desc, const unsigned long long* partials, int wgpg, int fg,
                                      int slot_cnt, const long long* parent_full, long long* full, const int* ctl,
                                      const void* link, const int* nvb, const uint8_t* tree_fmask,
                                      const double* qscale, const void* params, int nbt, int max_blocks,
-                                     int* ctl_next, const float* edges, int max_next_nodes, void* part,
-                                     void* next_link, void* tree, int tree_capacity, void* nsplit, int* ticket,
-                                     hipStream_t stream) {
+                                     const void* level_out, hipStream_t stream) {
   if (desc == nullptr) return kBadArg;
   const p2pdev::P2PDesc d = *reinterpret_cast<const p2pdev::P2PDesc*>(desc);
   const SplitParams p = *reinterpret_cast<const SplitParams*>(params);
@@ -3541,22 +3508,19 @@ H2OMX_API int h2omx_reduce_split_p2p(const void* desc, const unsigned long long*
   if ((int64_t)2 * slot_cnt * p.F * (int64_t)sizeof(FeatBest) > d.cap / 2) return kBadArg;
   const int nb = (int)std::min<int64_t>(items, std::min(std::max(max_blocks, 1), p2pdev::kMaxBlocks));
   const NodeLink* lk = reinterpret_cast<const NodeLink*>(link);
-  const LevelFin fin = make_fin(ctl_next, edges, max_next_nodes, part, next_link, tree, tree_capacity, nsplit, ticket);
-  const bool with_fin = ticket != nullptr;
-  if (with_fin && nsplit == nullptr) return kBadArg;
-#define LAUNCH_RSP(NB)                                                                                             \
-  if (p.catf != nullptr && with_fin)                                                                              \
-    hipLaunchKernelGGL((reduce_split_p2p_kernel<NB, true, true>), dim3(nb), dim3(1024), 0, stream, d, partials,   \
-                       wgpg, fg, slot_cnt, parent_full, full, ctl, lk, nvb, tree_fmask, qscale, p, fin);          \
-  else if (p.catf != nullptr)                                                                                     \
-    hipLaunchKernelGGL((reduce_split_p2p_kernel<NB, true>), dim3(nb), dim3(1024), 0, stream, d, partials, wgpg,   \
-                       fg, slot_cnt, parent_full, full, ctl, lk, nvb, tree_fmask, qscale, p, fin);                \
-  else if (with_fin)                                                                                              \
-    hipLaunchKernelGGL((reduce_split_p2p_kernel<NB, false, true>), dim3(nb), dim3(1024), 0, stream, d, partials,  \
-                       wgpg, fg, slot_cnt, parent_full, full, ctl, lk, nvb, tree_fmask, qscale, p, fin);          \
-  else                                                                                                            \
-    hipLaunchKernelGGL((reduce_split_p2p_kernel<NB, false>), dim3(nb), dim3(1024), 0, stream, d, partials, wgpg,  \
-                       fg, slot_cnt, parent_full, full, ctl, lk, nvb, tree_fmask, qscale, p, fin)
+  const bool with_fin = level_out != nullptr;
+  LevelOut lv{};
+  if (with_fin && !copy_level_out(lv, level_out)) return kBadArg;
+#define LAUNCH_RSPK(NB, CAT, FIN)                                                                                  \
+  hipLaunchKernelGGL((reduce_split_p2p_kernel<NB, CAT, FIN>), dim3(nb), dim3(1024), 0, stream, d, partials, wgpg, \
+                     fg, slot_cnt, parent_full, full, ctl, lk, nvb, tree_fmask, qscale, p, lv)
+#define LAUNCH_RSP(NB)                                               \
+  do {                                                               \
+    if (p.catf != nullptr && with_fin) LAUNCH_RSPK(NB, true, true);  \
+    else if (p.catf != nullptr) LAUNCH_RSPK(NB, true, false);        \
+    else if (with_fin) LAUNCH_RSPK(NB, false, true);                 \
+    else LAUNCH_RSPK(NB, false, false);                              \
+  } while (0)
   switch (nbt) {
     case 32: LAUNCH_RSP(32); break;
     case 64: LAUNCH_RSP(64); break;
@@ -3565,75 +3529,54 @@ H2OMX_API int h2omx_reduce_split_p2p(const void* desc, const unsigned long long*
     default: return kBadArg;
   }
 #undef LAUNCH_RSP
+#undef LAUNCH_RSPK
   return launch_status();
 }
 
-// level finalisation from per-node splits: one workgroup for small levels,
-// count / scan / write tiles (lf_*_kernel) when the level can hold more than
-// LF_MB_NODES nodes and the caller passed a tile scratch (>= max_nodes / 1024 + 1 ints)
+// level finalisation from the per-node splits in lv.nsplit: one workgroup for
+// small levels, count / scan / write tiles (lf_*_kernel) when the level can hold
+// more than LF_MB_NODES nodes and the caller passed a tile scratch
+// (>= max_nodes / 1024 + 1 ints)
 constexpr int LF_MB_NODES = 8192;
-static void level_finalize_launch(const NodeSplit* ns, const int* ctl, int* ctl_next, const SplitParams& p,
-                                  const float* edges, const int* nvb, int nbt, int max_next_nodes, void* part,
-                                  void* next_link, void* tree, int tree_capacity, int max_nodes, int* tiles,
-                                  hipStream_t stream) {
-  PartInfo* pi = reinterpret_cast<PartInfo*>(part);
-  NodeLink* nl = reinterpret_cast<NodeLink*>(next_link);
-  TreeNode* tr = reinterpret_cast<TreeNode*>(tree);
+static void level_finalize_launch(const int* ctl, const SplitParams& p, int nbt, const LevelOut& lv, int max_nodes,
+                                  int* tiles, hipStream_t stream) {
   if (tiles == nullptr || max_nodes <= LF_MB_NODES) {
-    hipLaunchKernelGGL(level_finalize_kernel, dim3(1), dim3(1024), 0, stream, ns, ctl, ctl_next, p, edges, nvb, nbt,
-                       max_next_nodes, pi, nl, tr, tree_capacity);
+    hipLaunchKernelGGL(level_finalize_kernel, dim3(1), dim3(1024), 0, stream, ctl, p, nbt, lv);
     return;
   }
   const int nt = (max_nodes + LF_TILE - 1) / LF_TILE;
-  hipLaunchKernelGGL(lf_count_kernel, dim3(nt), dim3(LF_TILE), 0, stream, ns, ctl, p, tiles);
-  hipLaunchKernelGGL(lf_scan_kernel, dim3(1), dim3(1024), 0, stream, tiles, nt, ctl, ctl_next, max_next_nodes);
-  hipLaunchKernelGGL(lf_write_kernel, dim3(nt), dim3(LF_TILE), 0, stream, ns, ctl, p, edges, nvb, nbt, max_next_nodes,
-                     pi, nl, tr, tree_capacity, tiles);
+  hipLaunchKernelGGL(lf_count_kernel, dim3(nt), dim3(LF_TILE), 0, stream, ctl, p, lv, tiles);
+  hipLaunchKernelGGL(lf_scan_kernel, dim3(1), dim3(1024), 0, stream, tiles, nt, ctl, lv);
+  hipLaunchKernelGGL(lf_write_kernel, dim3(nt), dim3(LF_TILE), 0, stream, ctl, p, nbt, lv, tiles);
 }
 
-H2OMX_API int h2omx_level_finalize(const void* fbest, const int* ctl, int* ctl_next, const void* params,
-                                   const float* edges, const int* nvb, int nbt, int max_next_nodes, void* part,
-                                   void* next_link, void* tree, int tree_capacity, void* nsplit,
-                                   int max_nodes, int* tiles, hipStream_t stream) {
+// fbest == nullptr: lv.nsplit already holds the level's records (direct
+// levels: seg_direct writes them), no per-node arg-max
+H2OMX_API int h2omx_level_finalize(const void* fbest, const int* ctl, const void* params, int nbt,
+                                   const void* level_out, int max_nodes, int* tiles, hipStream_t stream) {
   const SplitParams p = *reinterpret_cast<const SplitParams*>(params);
-  NodeSplit* ns = reinterpret_cast<NodeSplit*>(nsplit);
-  if (max_nodes <= 64) {   // one launch: the per-node arg-max inside the finalisation
-    hipLaunchKernelGGL(node_best_finalize_kernel, dim3(1), dim3(1024), 0, stream,
-                       reinterpret_cast<const FeatBest*>(fbest), ctl, ctl_next, p, edges, nvb, nbt, max_next_nodes,
-                       reinterpret_cast<PartInfo*>(part), reinterpret_cast<NodeLink*>(next_link),
-                       reinterpret_cast<TreeNode*>(tree), tree_capacity, ns);
+  LevelOut lv{};
+  if (!copy_level_out(lv, level_out)) return kBadArg;
+  const FeatBest* fb = reinterpret_cast<const FeatBest*>(fbest);
+  if (fb != nullptr && max_nodes <= 64) {   // one launch: the per-node arg-max inside the finalisation
+    hipLaunchKernelGGL(node_best_finalize_kernel, dim3(1), dim3(1024), 0, stream, fb, ctl, p, nbt, lv);
     return launch_status();
   }
-  hipLaunchKernelGGL(node_best_kernel, dim3(max_nodes), dim3(64), 0, stream, reinterpret_cast<const FeatBest*>(fbest),
-                     ctl, p.F, ns);
-  level_finalize_launch(ns, ctl, ctl_next, p, edges, nvb, nbt, max_next_nodes, part, next_link, tree, tree_capacity,
-                        max_nodes, tiles, stream);
+  if (fb != nullptr) hipLaunchKernelGGL(node_best_kernel, dim3(max_nodes), dim3(64), 0, stream, fb, ctl, p.F, lv.nsplit);
+  level_finalize_launch(ctl, p, nbt, lv, max_nodes, tiles, stream);
   return launch_status();
 }
 
-template <int MODE>
-__device__ void level_fin_records(const FeatBest* __restrict__ fbest, const int* __restrict__ ctl, const SplitParams& p,
-                                  const int* __restrict__ nvb, int nbt, const LevelFin& fin) {
-  const int n = ctl[CTL_N];
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, nw = blockDim.x >> 6;
-  for (int node = wid; node < n; node += nw) node_best_wave<MODE>(fbest, p.F, node, lane, fin.nsplit);
-  __syncthreads();
-  level_finalize_body(fin.nsplit, ctl, fin.ctl_next, p, fin.edges, nvb, nbt, fin.max_next_nodes, fin.part,
-                      fin.next_link, fin.tree, fin.tree_capacity);
-}
-
 // N-rank level finalisation (after h2omx_reduce_split_p2p, same desc)
-H2OMX_API int h2omx_node_best_finalize_p2p(const void* desc, const int* ctl, int* ctl_next, const void* params,
-                                           const float* edges, const int* nvb, int nbt, int max_next_nodes,
-                                           void* part, void* next_link, void* tree, int tree_capacity,
-                                           void* nsplit, hipStream_t stream) {
+H2OMX_API int h2omx_node_best_finalize_p2p(const void* desc, const int* ctl, const void* params, int nbt,
+                                           const void* level_out, hipStream_t stream) {
   if (desc == nullptr) return kBadArg;
   const p2pdev::P2PDesc d = *reinterpret_cast<const p2pdev::P2PDesc*>(desc);
   if (d.world < 2 || d.world > p2pdev::kMaxRanks || d.rank < 0 || d.rank >= d.world) return kBadArg;
   const SplitParams p = *reinterpret_cast<const SplitParams*>(params);
-  hipLaunchKernelGGL(node_best_finalize_p2p_kernel, dim3(1), dim3(1024), 0, stream, d, ctl, ctl_next, p, edges, nvb,
-                     nbt, max_next_nodes, reinterpret_cast<PartInfo*>(part), reinterpret_cast<NodeLink*>(next_link),
-                     reinterpret_cast<TreeNode*>(tree), tree_capacity, reinterpret_cast<NodeSplit*>(nsplit));
+  LevelOut lv{};
+  if (!copy_level_out(lv, level_out)) return kBadArg;
+  hipLaunchKernelGGL(node_best_finalize_p2p_kernel, dim3(1), dim3(1024), 0, stream, d, ctl, p, nbt, lv);
   return launch_status();
 }
 
@@ -3649,7 +3592,8 @@ static int partition_launch(const uint8_t* codes, int64_t npad, int* nid, const 
   // level prologue: this level is finalised inside the launch (ctl_next / part are then outputs)
   LevelPro lpz{};
   if (lpp) lpz = *lpp;
-  if (lpp && (lpz.fbest == nullptr || lpz.nsplit == nullptr || lpz.ctl_next != ctl_next || (const void*)lpz.part != part))
+  if (lpp && (lpz.fbest == nullptr || lpz.lv.nsplit == nullptr || lpz.lv.ctl_next != ctl_next ||
+              (const void*)lpz.lv.part != part))
     return kBadArg;
   // nidm bit 0: nid is an int16 stream, bit 1: nid_out is (fused pipeline; distinct buffers)
   if (nidm != 0 && nid_out == nid) return kBadArg;
@@ -3726,18 +3670,15 @@ H2OMX_API int h2omx_partition_final(const uint8_t* codes, int64_t npad, const in
 
 // h2omx_partition_route / h2omx_partition_final that also finalise the level
 // they route (level prologue, LevelPro) - each replaces h2omx_level_finalize +
-// the partition for levels of <= 64 nodes.  part and ctl_next are written by
-// block 0.
+// the partition for levels of <= 64 nodes.  part and ctl_next (the ones of
+// level_out) are written by block 0.
 H2OMX_API int h2omx_partition_route_fin(const uint8_t* codes, int64_t npad, const int* nid_in, int* nid_out, void* part,
                                         int nbt, const int* ctl_cur, int* ctl_next, int blocks, short* slot16,
-                                        int nidm, const void* fbest, const void* params, const float* edges,
-                                        const int* nvb, int max_next_nodes, void* next_link, void* tree,
-                                        int tree_capacity, void* nsplit, int max_nodes, hipStream_t stream) {
+                                        int nidm, const void* fbest, const void* params, const void* level_out,
+                                        int max_nodes, hipStream_t stream) {
   if (slot16 == nullptr) return kBadArg;
   LevelPro lp{};
-  if (!make_pro(lp, fbest, params, ctl_next, edges, nvb, max_next_nodes, part, next_link, tree, tree_capacity, nsplit,
-                max_nodes))
-    return kBadArg;
+  if (!make_pro(lp, fbest, params, level_out, max_nodes)) return kBadArg;
   return partition_launch(codes, npad, const_cast<int*>(nid_in), part, nbt, nullptr, nullptr, nullptr, nullptr, 0,
                           nullptr, ctl_cur, ctl_next, 0, blocks, 0, slot16, nid_out, 0, stream, nullptr, nullptr,
                           nullptr, nidm, nullptr, &lp);
@@ -3747,13 +3688,10 @@ H2OMX_API int h2omx_partition_final_fin(const uint8_t* codes, int64_t npad, cons
                                         int nbt, const float* g, const float* h, const float* w, const double* qscale,
                                         int cap, unsigned long long* leaf_acc, const int* ctl_cur, int* ctl_next,
                                         int blocks, const float* Fm, const float* y, const void* gparams, int nidm,
-                                        const uint8_t* y8, const void* fbest, const void* params, const float* edges,
-                                        const int* nvb, int max_next_nodes, void* next_link, void* tree,
-                                        int tree_capacity, void* nsplit, int max_nodes, hipStream_t stream) {
+                                        const uint8_t* y8, const void* fbest, const void* params,
+                                        const void* level_out, int max_nodes, hipStream_t stream) {
   LevelPro lp{};
-  if (!make_pro(lp, fbest, params, ctl_next, edges, nvb, max_next_nodes, part, next_link, tree, tree_capacity, nsplit,
-                max_nodes))
-    return kBadArg;
+  if (!make_pro(lp, fbest, params, level_out, max_nodes)) return kBadArg;
   return partition_launch(codes, npad, const_cast<int*>(nid_in), part, nbt, g, h, w, qscale, cap, leaf_acc, ctl_cur,
                           ctl_next, cap, blocks, 1, nullptr, nid_out, 1, stream, Fm, y,
                           reinterpret_cast<const GradParams*>(gparams), nidm, y8, &lp);
@@ -4593,7 +4531,7 @@ __global__ __launch_bounds__(256) void node_close_kernel(
 // DRF 10M x 100, profiles/drf_depth20_level_breakdown.txt) while the rows of
 // all nodes are only n x (eligible F) bytes.  Exact int64 sums of the same
 // quantised rows: bit-identical splits to the subtraction path.  Writes the
-// node's NodeSplit directly (level_finalize_ns follows).
+// node's NodeSplit directly (level_finalize without fbest follows).
 // ---------------------------------------------------------------------------
 constexpr int DIRECT_LDS_BYTES = 96 * 1024;   // histogram batch (G and S int64 planes)
 constexpr int DIRECT_WAVES = 4;   // waves per node workgroup (<= 4)
@@ -6146,17 +6084,6 @@ H2OMX_API int h2omx_direct_dp(int phase, const uint8_t* codes_rm, int fp, const 
     default: return kBadArg;
   }
 #undef LAUNCH_DDP
-  return launch_status();
-}
-
-// level_finalize from per-node splits already in nsplit (direct mode)
-H2OMX_API int h2omx_level_finalize_ns(const void* nsplit, const int* ctl, int* ctl_next, const void* params,
-                                      const float* edges, const int* nvb, int nbt, int max_next_nodes, void* part,
-                                      void* next_link, void* tree, int tree_capacity, int max_nodes, int* tiles,
-                                      hipStream_t stream) {
-  const SplitParams p = *reinterpret_cast<const SplitParams*>(params);
-  level_finalize_launch(reinterpret_cast<const NodeSplit*>(nsplit), ctl, ctl_next, p, edges, nvb, nbt, max_next_nodes,
-                        part, next_link, tree, tree_capacity, max_nodes, tiles, stream);
   return launch_status();
 }
 

@@ -27,8 +27,8 @@ import torch
 from ... import ops
 from .binning import BinnedMatrix
 from ...utils.trace import PhaseTimer
-from .structs import (FEAT_BEST_BYTES, NODE_LINK_BYTES, PART_INFO_BYTES, TREE_NODE_DTYPE, GradParams,
-                      SplitParams, check_layout, interaction_masks)
+from .structs import (FEAT_BEST_BYTES, NODE_LINK_BYTES, NODE_SPLIT_BYTES, PART_INFO_BYTES, TREE_NODE_DTYPE, GradParams,
+                      LevelOut, SplitParams, check_layout, interaction_masks)
 
 
 @dataclass
@@ -486,6 +486,13 @@ class HipTreeBuilder:
         sp.frange = self._frange.data_ptr() if p.hist_mode else None
         return ctypes.addressof(sp)
 
+    def _level_out(self, ctl_nxt, part, nl, nsplit, next_nodes: int) -> LevelOut:
+        """Where a level's finalisation writes (callers pass ``ctypes.addressof``
+        of it and keep it alive until the launch that reads it is enqueued)."""
+        P = ops.P
+        return LevelOut(P(ctl_nxt), P(self.bm.edges), P(self.bm.nvb), P(part), P(nl), P(self.tree_buf), P(nsplit),
+                        next_nodes, self.capacity)
+
     def _cat_level(self, max_nodes: int) -> None:
         """Point SplitParams::fbcat at a [max_nodes][F][8] scratch for this level."""
         if self.catf is not None:
@@ -601,15 +608,14 @@ class HipTreeBuilder:
             if not last:
                 nl = self._buf(f"link{nxt}", next_nodes * NODE_LINK_BYTES // 4, torch.int32)
                 link[nxt] = nl
-            nsplit = self._buf("nsplit", max_nodes * 9, torch.float64)  # NodeSplit = 72 B
+            nsplit = self._buf("nsplit", max_nodes * NODE_SPLIT_BYTES // 8, torch.float64)
             # one-pass levels of <= 64 nodes finalise in the last workgroup of their
             # reduce + split scan (LevelFin in csrc/tree_kernels.hip)
             fin = rs and max_nodes <= 64 and ((fuse_p2p and self.FUSE_FIN)
                                               or (comm is None and self.FUSE_FIN_LOCAL and plan["passes"] == 1))
             if fin and getattr(self, "_fin_ticket", None) is None:
                 self._fin_ticket = torch.zeros((1,), dtype=torch.int32, device=self.dev)   # each launch leaves 0
-            fin_args = (P(ctl_nxt), P(bm.edges), next_nodes, P(part), P(nl), P(self.tree_buf), self.capacity,
-                        P(nsplit), P(self._fin_ticket if fin else None))
+            lvo = self._level_out(ctl_nxt, part, nl, nsplit, next_nodes)
             # the level is finalised in the prologue of the launch that routes its rows:
             # "hist" (level d + 1's routed histogram, one pass), "route" or "final"
             pro = None
@@ -629,9 +635,7 @@ class HipTreeBuilder:
                     ops.check(lib.h2omx_reduce_split_p2p(p2p.desc_ptr, P(partials), wgpg, fg, slot_cnt, P(full_prev),
                                                          P(full_cur), P(ctl_cur), P(link[cur]), P(bm.nvb),
                                                          P(tree_fmask), P(self.qscale), spp, nbt,
-                                                         self.P2P_BLOCKS,
-                                                         *(fin_args if fin else (None, None, 0, None, None, None, 0,
-                                                                                 None, None)), st),
+                                                         self.P2P_BLOCKS, ctypes.addressof(lvo) if fin else None, st),
                               "reduce_split_p2p")
                     comm.stats["p2p_calls"] += 1
                     comm.stats["p2p_bytes"] += max_slots * self.per_node * 8
@@ -640,7 +644,8 @@ class HipTreeBuilder:
                         raise RuntimeError("reduce_split_fin: multi-pass level")   # excluded by fin
                     ops.check(lib.h2omx_reduce_split_fin(P(partials), wgpg, fg, slot_cnt, P(full_prev), P(full_cur),
                                                          P(ctl_cur), P(link[cur]), P(bm.nvb), P(tree_fmask),
-                                                         P(self.qscale), spp, nbt, P(fbest), *fin_args, st),
+                                                         P(self.qscale), spp, nbt, P(fbest), ctypes.addressof(lvo),
+                                                         P(self._fin_ticket), st),
                               "reduce_split_fin")
                 elif rs:
                     ops.check(lib.h2omx_reduce_split(P(partials), wgpg, fg, slot_lo, slot_cnt, P(full_prev),
@@ -716,26 +721,20 @@ class HipTreeBuilder:
                     pass   # finalised inside the reduce launch
                 elif pro is not None:
                     # finalised by the launch that routes this level (a snapshot of the
-                    # level's SplitParams and its buffers travel to the next iteration)
+                    # level's SplitParams, its LevelOut and its buffers travel to the next
+                    # iteration)
                     spc = type(sp).from_buffer_copy(sp)
-                    pro_tail = (P(fbest), ctypes.addressof(spc), P(bm.edges))
-                    pro_rest = (next_nodes, P(nl), P(self.tree_buf), self.capacity, P(nsplit), max_nodes)
+                    pro_args = (P(fbest), ctypes.addressof(spc), ctypes.addressof(lvo), max_nodes)
                     if pro == "hist":
-                        pend = dict(args=pro_tail + pro_rest,
-                                    keep=(spc, fbest, nl, nsplit, self._bufs.get("fbcat")))
+                        pend = dict(args=pro_args, keep=(spc, lvo, fbest, nl, nsplit, self._bufs.get("fbcat")))
                 elif fuse_p2p:
                     # waits for every rank's share of the split records (all-gathered
                     # into this rank's split table by reduce_split_p2p)
-                    ops.check(lib.h2omx_node_best_finalize_p2p(p2p.desc_ptr, P(ctl_cur), P(ctl_nxt), spp, P(bm.edges),
-                                                               P(bm.nvb), nbt, next_nodes, P(part), P(nl),
-                                                               P(self.tree_buf), self.capacity, P(nsplit), st),
-                              "node_best_finalize_p2p")
+                    ops.check(lib.h2omx_node_best_finalize_p2p(p2p.desc_ptr, P(ctl_cur), spp, nbt,
+                                                               ctypes.addressof(lvo), st), "node_best_finalize_p2p")
                 else:
-                    ops.check(lib.h2omx_level_finalize(P(fbest), P(ctl_cur), P(ctl_nxt), spp, P(bm.edges),
-                                                       P(bm.nvb), nbt, next_nodes, P(part), P(nl),
-                                                       P(self.tree_buf), self.capacity, P(nsplit), max_nodes,
-                                                       self._lf_tiles(max_nodes),
-                                                       st), "level_finalize")
+                    ops.check(lib.h2omx_level_finalize(P(fbest), P(ctl_cur), spp, nbt, ctypes.addressof(lvo),
+                                                       max_nodes, self._lf_tiles(max_nodes), st), "level_finalize")
             # leaves that can retire at this level: gids [base, base + n + n_next)
             win = min(3 * max_nodes, self.capacity)
             with T("partition"):
@@ -755,7 +754,7 @@ class HipTreeBuilder:
                                (3 if leaf16 else 1) if nid16 else 0,
                                P(rg[3] if rg else None))
                     if pro == "final":
-                        ops.check(lib.h2omx_partition_final_fin(*pf_args, *pro_tail, P(bm.nvb), *pro_rest, st),
+                        ops.check(lib.h2omx_partition_final_fin(*pf_args, *pro_args, st),
                                   "partition_final_fin")
                     else:
                         ops.check(lib.h2omx_partition_final(*pf_args, st), "partition_final")
@@ -763,7 +762,7 @@ class HipTreeBuilder:
                     pr_args = (P(bm.codes), bm.npad, P(nid_buf[d % 2]), P(nid_buf[(d + 1) % 2]), P(part), nbt,
                                P(ctl_cur), P(ctl_nxt), self.part_blocks, P(self.slot16), 3 if nid16 else 0)
                     if pro == "route":
-                        ops.check(lib.h2omx_partition_route_fin(*pr_args, *pro_tail, P(bm.nvb), *pro_rest, st),
+                        ops.check(lib.h2omx_partition_route_fin(*pr_args, *pro_args, st),
                                   "partition_route_fin")
                     else:
                         ops.check(lib.h2omx_partition_route(*pr_args, st), "partition_route")
@@ -1034,7 +1033,7 @@ class HipTreeBuilder:
                 sp.depth = d
                 sp.children_leaves = 1 if last else 0
                 next_nodes = 2 * max_nodes
-                nsplit = B("nsplit", max_nodes * 9, torch.float64)
+                nsplit = B("nsplit", max_nodes * NODE_SPLIT_BYTES // 8, torch.float64)
                 part = B("part", max_nodes * PART_INFO_BYTES // 4, i32)
                 nl = None
                 if not last:
@@ -1093,11 +1092,10 @@ class HipTreeBuilder:
                                                    P(nsplit), gs["pos"], P(ecodes), ecs, P(nodeq), P(ccol),
                                                    P(cpos_cur), plane, st),
                               "seg_direct")
-                ops.check(lib.h2omx_level_finalize_ns(P(nsplit), P(ctl_cur), P(ctl_nxt), spp, P(bm.edges),
-                                                      P(bm.nvb), nbt, next_nodes, P(part), P(nl), P(self.tree_buf),
-                                                      self.capacity, max_nodes,
-                                                      self._lf_tiles(max_nodes), st),
-                          "level_finalize_ns")
+                # (no fbest: seg_direct wrote the level's records into nsplit)
+                lvo = self._level_out(ctl_nxt, part, nl, nsplit, next_nodes)
+                ops.check(lib.h2omx_level_finalize(None, P(ctl_cur), spp, nbt, ctypes.addressof(lvo), max_nodes,
+                                                   self._lf_tiles(max_nodes), st), "level_finalize")
                 if not last and next_nodes > self.SYNC_NODE_CAP:
                     self._count_ahead(ctl_nxt, nxt)
                 idx_in, _ = route(d, last, max_nodes, next_nodes, part, nl, seg_start, seg_cnt, pc_first, ctl_cur,
@@ -1153,11 +1151,10 @@ class HipTreeBuilder:
             if not last:
                 nl = B(f"link{nxt}", next_nodes * NODE_LINK_BYTES // 4, i32)
                 link[nxt] = nl
-            nsplit = B("nsplit", max_nodes * 9, torch.float64)
-            ops.check(lib.h2omx_level_finalize(P(fbest), P(ctl_cur), P(ctl_nxt), spp, P(bm.edges), P(bm.nvb), nbt,
-                                               next_nodes, P(part), P(nl), P(self.tree_buf), self.capacity,
-                                               P(nsplit), max_nodes, self._lf_tiles(max_nodes), st),
-                      "level_finalize")
+            nsplit = B("nsplit", max_nodes * NODE_SPLIT_BYTES // 8, torch.float64)
+            lvo = self._level_out(ctl_nxt, part, nl, nsplit, next_nodes)
+            ops.check(lib.h2omx_level_finalize(P(fbest), P(ctl_cur), spp, nbt, ctypes.addressof(lvo), max_nodes,
+                                               self._lf_tiles(max_nodes), st), "level_finalize")
             if not last and next_nodes > self.SYNC_NODE_CAP:
                 self._count_ahead(ctl_nxt, nxt)
             idx_in, built_zeroed = route(d, last, max_nodes, next_nodes, part, nl, seg_start, seg_cnt, pc_first,

@@ -12,6 +12,7 @@ TREE_NODE_DTYPE = np.dtype([
 NODE_LINK_BYTES = 16
 PART_INFO_BYTES = 32
 FEAT_BEST_BYTES = 64
+NODE_SPLIT_BYTES = 72
 
 
 class SplitParams(ctypes.Structure):
@@ -64,6 +65,15 @@ class GradParams(ctypes.Structure):
     ]
 
 
+class LevelOut(ctypes.Structure):
+    """Where a level's finalisation writes (LevelOut in csrc/tree_kernels.hip)."""
+    _fields_ = [
+        ("ctl_next", ctypes.c_void_p), ("edges", ctypes.c_void_p), ("nvb", ctypes.c_void_p),
+        ("part", ctypes.c_void_p), ("next_link", ctypes.c_void_p), ("tree", ctypes.c_void_p),
+        ("nsplit", ctypes.c_void_p), ("max_next_nodes", ctypes.c_int), ("tree_capacity", ctypes.c_int),
+    ]
+
+
 def interaction_masks(sets, F: int) -> np.ndarray:
     """Per-feature bit masks of the interaction sets holding it (uint64; 0 =
     unlisted: such a feature only interacts with itself).  ``sets`` holds
@@ -110,8 +120,8 @@ def check_layout(lib) -> None:
     sizes = (ctypes.c_int * 8)()
     lib.h2omx_tree_sizes(sizes)
     want = [ctypes.sizeof(SplitParams), FEAT_BEST_BYTES, NODE_LINK_BYTES, PART_INFO_BYTES,
-            TREE_NODE_DTYPE.itemsize, ctypes.sizeof(GradParams)]
-    got = list(sizes)[:6]
+            TREE_NODE_DTYPE.itemsize, ctypes.sizeof(GradParams), ctypes.sizeof(LevelOut), NODE_SPLIT_BYTES]
+    got = list(sizes)
     if got != want:
         raise RuntimeError(f"tree kernel ABI mismatch: kernel sizes {got} != python {want}")
 

@@ -24,20 +24,19 @@ TREE_SIGS = {
     "h2omx_hist_build_grad": "PLPPPIIIIIIIIIPPPPPPIPPIIIPS",
     "h2omx_split_find": "PPPPPPPPPIIPS",
     "h2omx_reduce_split": "PIIIIPPPPPPPPIPS",
-    "h2omx_reduce_split_p2p": "PPIIIPPPPPPPPIIPPIPPPIPPS",
-    "h2omx_reduce_split_fin": "PIIIPPPPPPPPIPPPIPPPIPPS",
-    "h2omx_node_best_finalize_p2p": "PPPPPPIIPPPIPS",
+    "h2omx_reduce_split_p2p": "PPIIIPPPPPPPPIIPS",
+    "h2omx_reduce_split_fin": "PIIIPPPPPPPPIPPPS",
+    "h2omx_node_best_finalize_p2p": "PPPIPS",
     "h2omx_leaf_finalize_p2p": "PPPPPPIIPIIPPLPS",
-    "h2omx_level_finalize": "PPPPPPIIPPPIPIPS",
+    "h2omx_level_finalize": "PPPIPIPS",
     "h2omx_partition": "PLPPIPPPPIPPPIIIPS",
     "h2omx_partition_blocks": "",
     "h2omx_partition_final": "PLPPPIPPPPIPPPIPPPIPS",
     "h2omx_partition_route": "PLPPPIPPIPIS",
-    # level finalisation as the consumer launch's prologue (+ fbest, params, edges,
-    # [nvb,] max_next_nodes, next_link, tree, tree_capacity, nsplit, max_nodes)
-    "h2omx_hist_build_route_fin": "PLPPPPPPPIIIIIIIIPIPPPPIPPIPIS",
-    "h2omx_partition_route_fin": "PLPPPIPPIPIPPPPIPPIPIS",
-    "h2omx_partition_final_fin": "PLPPPIPPPPIPPPIPPPIPPPPPIPPIPIS",
+    # level finalisation as the consumer launch's prologue (+ fbest, params, level_out, max_nodes)
+    "h2omx_hist_build_route_fin": "PLPPPPPPPIIIIIIIIPIPPPPIS",
+    "h2omx_partition_route_fin": "PLPPPIPPIPIPPPIS",
+    "h2omx_partition_final_fin": "PLPPPIPPPPIPPPIPPPIPPPPIS",
     "h2omx_leaf_reduce": "PIIPS",
     "h2omx_boost_update": "PPPLLPPPPPPPLPIPIPPIIPPS",
     "h2omx_apply_tree": "PLPPS",
@@ -68,7 +67,6 @@ TREE_SIGS = {
     "h2omx_seg_direct": "PIPPPPPPPPPIPIIIPIPPPPIPIPPPLS",
     "h2omx_seg_colmajor": "PIIPILPLS",
     "h2omx_codes_rowmajor": "PLILPIS",
-    "h2omx_level_finalize_ns": "PPPPPPIIPPPIIPS",
     "h2omx_direct_dp_stride": "PI",
     "h2omx_direct_dp": "IPIPPPPPPPPPPIIIPPIPS",
 }

@@ -84,10 +84,10 @@ def test_p2p_allreduce_two_ranks_one_gpu():
         assert outs[0]["checks"][k] == outs[1]["checks"][k]
 
 
-def _bench(nproc, extra, env_extra, timeout=300):
+def _bench(nproc, extra, env_extra, timeout=300, script="bench.py"):
     env = dict(os.environ, OMP_NUM_THREADS="2", **env_extra)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={nproc}",
-           "--master-addr", "127.0.0.1", "--master-port", str(_port()), os.path.join(ROOT, "bench.py"),
+           "--master-addr", "127.0.0.1", "--master-port", str(_port()), os.path.join(ROOT, script),
            "--gpus", str(nproc), "--steps", "3", "--warmup", "1", "--full"] + extra
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=timeout)
     assert r.returncode == 0, r.stderr[-4000:]
@@ -96,24 +96,50 @@ def _bench(nproc, extra, env_extra, timeout=300):
     return json.loads(lines[0])
 
 
+STRONG = ["--rows", "300000", "--scaling", "strong", "--instrument-steps", "2", "--fit-trees", "0"]
+
+
+@pytest.fixture(scope="module")
+def one_rank(tmp_path_factory):
+    """The 1-rank run both 2-rank tests compare against: (result, trees file)."""
+    one = tmp_path_factory.mktemp("one_rank") / "one.npy"
+    return _bench(1, STRONG + ["--dump-trees", str(one)], {}), one
+
+
 @pytest.mark.gpu
-def test_gbm_two_ranks_p2p_one_graph_reproduces_one_rank(tmp_path):
+def test_gbm_two_ranks_p2p_one_graph_reproduces_one_rank(tmp_path, one_rank):
     """Strong scaling with the P2P collectives captured in the step graph: zero
     host-issued collectives per timed tree, trees bit-identical to one rank."""
     import numpy as np
 
     from test_bench_contract import _assert_same_trees
 
-    extra = ["--rows", "300000", "--scaling", "strong", "--instrument-steps", "2", "--fit-trees", "0"]
-    one, two = tmp_path / "one.npy", tmp_path / "two.npy"
-    o1 = _bench(1, extra + ["--dump-trees", str(one)], {})
-    o2 = _bench(2, extra + ["--dump-trees", str(two)], {"H2OMX_DIST_BACKEND": "gloo", "H2OMX_P2P": "1"})
+    (o1, one), two = one_rank, tmp_path / "two.npy"
+    o2 = _bench(2, STRONG + ["--dump-trees", str(two)], {"H2OMX_DIST_BACKEND": "gloo", "H2OMX_P2P": "1"})
     assert o2["collective_transport"].startswith("p2p"), o2["collective_transport"]
     assert o1["graph_replay"] and o2["graph_replay"]
     assert o2["collectives_host_issued_per_tree"] == 0
     # device-side exchanges, each inside a kernel the 1-rank step also runs:
     # 5 fused level reduce + split scans and the leaf finalisation
     assert o2["allreduce_calls_per_tree"] == 6
+    _assert_same_trees(np.load(one), np.load(two), exact_values=True)
+    assert o1["train_auc"] == o2["train_auc"]
+
+
+@pytest.mark.gpu
+def test_gbm_two_ranks_p2p_separate_finalisation_reproduces_one_rank(tmp_path, one_rank):
+    """The same run with HipTreeBuilder.FUSE_FIN off: every level's finalisation
+    is its own launch after the exchange (h2omx_node_best_finalize_p2p; the path
+    levels of more than 64 nodes take) - trees bit-identical to one rank."""
+    import numpy as np
+
+    from test_bench_contract import _assert_same_trees
+
+    (o1, one), two = one_rank, tmp_path / "two.npy"
+    o2 = _bench(2, STRONG + ["--dump-trees", str(two)],
+                {"H2OMX_DIST_BACKEND": "gloo", "H2OMX_P2P": "1", "H2OMX_P2P_TIMEOUT_S": "10"},
+                script=os.path.join("tests", "_p2p_nofin_worker.py"))
+    assert o2["collective_transport"].startswith("p2p"), o2["collective_transport"]
     _assert_same_trees(np.load(one), np.load(two), exact_values=True)
     assert o1["train_auc"] == o2["train_auc"]
 
