@@ -940,6 +940,13 @@ constexpr int HB_PF = 1;     // feature code loads kept in flight per lane
 // conflict-free 7.3), at COP x the LDS per feature (fewer features per group)
 // NID16 (fused-routing levels): the previous / next node ids are int16 streams
 // (2 bytes a row each way instead of 4; padding rows hold INT16_MIN)
+// Histogram planes: the kernel builds F planes of valid-bin counts nvb[]; with
+// a plane table (plane_src, one rank: engine.py BUNDLE) plane p reads feature
+// plane plane_src[p] >= 0 of `codes`, or joint plane ~plane_src[p] of `joint`
+// (the mixed-radix code of several low-cardinality features, bundle_planes_kernel;
+// nvb = NBT - 1: one full-width slice).  reduce_split marginalises the joint
+// rows back into per-feature rows.  The fused routing and the level prologue
+// read the split features' own planes of `codes` either way.
 template <int NBT, int ROWS, int PKM, bool ROUTE, bool CMP, int COP = 1, bool NID16 = false>
 __global__ __launch_bounds__(1024) void hist_build_kernel(
     const uint8_t* __restrict__ codes, int64_t npad, const float* __restrict__ g, const float* __restrict__ s2,
@@ -947,7 +954,8 @@ __global__ __launch_bounds__(1024) void hist_build_kernel(
     const int* __restrict__ nvb, const double* __restrict__ qscale, uint32_t salt, int F, int fg, int n_groups,
     int wgpg, int slot_lo, int slot_cnt, const short* __restrict__ slot16, unsigned long long* __restrict__ pk_buf,
     unsigned long long* __restrict__ partials, const PartInfo* __restrict__ part_prev,
-    const int* __restrict__ ctl_prev, int* __restrict__ nid_out, int writer, GradFuse gf, LevelPro lp) {
+    const int* __restrict__ ctl_prev, int* __restrict__ nid_out, int writer, GradFuse gf, LevelPro lp,
+    const uint8_t* __restrict__ joint, const int* __restrict__ plane_src) {
   salt = (uint32_t)qscale[9];  // per-tree dither salt, written by tree_begin (graph-replay safe)
   extern __shared__ __attribute__((aligned(16))) unsigned long long lds64[];
   __shared__ int width_s[256], rep_s[256];
@@ -977,6 +985,11 @@ __global__ __launch_bounds__(1024) void hist_build_kernel(
   static_assert(COP == 1 || ((PKM == 1 || PKM == 3 || PKM == 6) && !ROUTE && !CMP), "copies: level-0 kernel only");
   const int hist_elems = slot_cnt * fg * NBT;
   const int lane = threadIdx.x & 63;
+  // codes of histogram plane f0 + fi (wave-uniform index: a scalar table load)
+  auto plane_codes = [&](int fi) -> const uint8_t* {
+    const int sp = plane_src ? plane_src[f0 + fi] : f0 + fi;
+    return sp >= 0 ? codes + (int64_t)sp * npad : joint + (int64_t)(~sp) * npad;
+  };
 
   for (int j = threadIdx.x; j < hist_elems * COP; j += blockDim.x) lds64[j] = 0ull;
   if (threadIdx.x < fg) {
@@ -1149,7 +1162,7 @@ __global__ __launch_bounds__(1024) void hist_build_kernel(
     // overlaps the (g, s) loads / gradient chain instead of following it
     uint32_t pf[HB_PF][ROWS / 4];
     auto load_codes = [&](int fi, uint32_t* cw) {
-      const uint8_t* cp = codes + (int64_t)(f0 + fi) * npad + r0;
+      const uint8_t* cp = plane_codes(fi) + r0;
       if constexpr (ROWS == 16) {
         const uint4 c4 = *reinterpret_cast<const uint4*>(cp);
         cw[0] = c4.x; cw[1] = c4.y; cw[2] = c4.z; cw[3] = c4.w;
@@ -1312,14 +1325,14 @@ __global__ __launch_bounds__(1024) void hist_build_kernel(
       uint4 pf[HB_PF];
 #pragma unroll
       for (int q = 0; q < HB_PF; ++q)
-        if (q < nf) pf[q] = *reinterpret_cast<const uint4*>(codes + (int64_t)(f0 + q) * npad + r0);
+        if (q < nf) pf[q] = *reinterpret_cast<const uint4*>(plane_codes(q) + r0);
       for (int fb = 0; fb < nf; fb += HB_PF) {
 #pragma unroll
         for (int q = 0; q < HB_PF; ++q) {
           const int fi = fb + q;
           if (fi < nf) {
             *reinterpret_cast<uint4*>(stc + lane * ROWS) = pf[q];
-            if (fi + HB_PF < nf) pf[q] = *reinterpret_cast<const uint4*>(codes + (int64_t)(f0 + fi + HB_PF) * npad + r0);
+            if (fi + HB_PF < nf) pf[q] = *reinterpret_cast<const uint4*>(plane_codes(fi + HB_PF) + r0);
             const int width = width_s[fi], rep = rep_s[fi];
             const int copy_off = (rep > 1) ? (lane % rep) * width : 0;
             const int na_slot = (rep > 1) ? width - 1 : NBT - 1;   // see the fold below
@@ -1934,6 +1947,29 @@ __device__ __forceinline__ void rs_reduce_row(const unsigned long long* __restri
   __syncthreads();
 }
 
+// Bundled feature: `row` holds the exact sums of its bundle's joint plane (code
+// = sum of digit_k * stride_k; a feature's digit is its bin, NA = its valid-bin
+// count = radix - 1).  Summing over the other digits leaves the feature's own
+// row: bin b < radix - 1 from digit b, the NA bin NBT - 1 from digit radix - 1,
+// every other bin zero - the int64 sums its own plane would have given.
+// Called by all threads of the workgroup.
+template <int NBT>
+__device__ __forceinline__ void rs_marginalise(long long (*row)[NBT], int stride, int radix) {
+  const int t = threadIdx.x;
+  long long jg = 0, js = 0;
+  if (t < NBT) { jg = row[0][t]; js = row[1][t]; }
+  __syncthreads();
+  if (t < NBT) { row[0][t] = 0; row[1][t] = 0; }
+  __syncthreads();
+  if (t < NBT && (jg != 0 || js != 0)) {
+    const int digit = (t / stride) % radix;
+    const int bin = digit == radix - 1 ? NBT - 1 : digit;
+    atomicAdd(reinterpret_cast<unsigned long long*>(&row[0][bin]), (unsigned long long)jg);
+    atomicAdd(reinterpret_cast<unsigned long long*>(&row[1][bin]), (unsigned long long)js);
+  }
+  __syncthreads();
+}
+
 // waves 0 / 1 of the block: split scan of the two children of `slot` for
 // feature f from the completed built row in LDS.  Returns false for a wave
 // without a node (waves >= 2, or a child beyond the level); otherwise `node`
@@ -2005,7 +2041,8 @@ __global__ __launch_bounds__(1024) void reduce_split_kernel(
     const unsigned long long* __restrict__ partials, int wgpg, int fg, int slot_lo, int slot_cnt,
     const long long* __restrict__ parent_full, long long* __restrict__ full, const int* __restrict__ ctl,
     const NodeLink* __restrict__ link, const int* __restrict__ nvb, const uint8_t* __restrict__ tree_fmask,
-    const double* __restrict__ qscale, SplitParams p, FeatBest* __restrict__ out, LevelFin fin) {
+    const double* __restrict__ qscale, SplitParams p, FeatBest* __restrict__ out, LevelFin fin,
+    const int* __restrict__ feat_plane) {
   __shared__ long long red[1024 / (NBT / 2)][NBT / 2][4];   // 32 KB
   __shared__ long long row[2][NBT];                         // exact (G_q, S_q) of the built slot
   const int s = blockIdx.x, f = blockIdx.y;
@@ -2013,7 +2050,12 @@ __global__ __launch_bounds__(1024) void reduce_split_kernel(
   const bool active = slot < ctl[CTL_SLOTS];   // whole workgroup
   if (!FIN && !active) return;
   if (active) {
-    rs_reduce_row<NBT>(partials, wgpg, fg, slot_cnt, s, f, red, row);
+    // feat_plane[f] = (plane position in the slabs, stride, radix); radix 0: the
+    // plane is the feature's own.  No table: plane f is feature f
+    int pos = f, stride = 0, radix = 0;
+    if (feat_plane != nullptr) { pos = feat_plane[3 * f]; stride = feat_plane[3 * f + 1]; radix = feat_plane[3 * f + 2]; }
+    rs_reduce_row<NBT>(partials, wgpg, fg, slot_cnt, s, pos, red, row);
+    if (radix > 0) rs_marginalise<NBT>(row, stride, radix);
     int node;
     WaveBest w;
     if (rs_scan_node<NBT, CAT>(row, slot, f, parent_full, full, ctl, link, nvb, tree_fmask, qscale, p, node, w) &&
@@ -3209,7 +3251,10 @@ static int hist_build_launch(const uint8_t* codes, int64_t npad, const float* g,
                              int rows_per_lane, int threads, const short* slot16, unsigned long long* pk_buf,
                              int pkm, unsigned long long* partials, const void* part_prev, const int* ctl_prev,
                              int* nid_out, int writer, hipStream_t stream, const GradFuse* gfp = nullptr,
-                             const LevelPro* lpp = nullptr) {
+                             const LevelPro* lpp = nullptr, const uint8_t* joint = nullptr,
+                             const int* plane_src = nullptr) {
+  // plane table (F = planes, nvb = the planes' valid bins): see hist_build_kernel
+  if ((joint == nullptr) != (plane_src == nullptr)) return kBadArg;
   const bool route = part_prev != nullptr;
   GradFuse gfz{};
   if (gfp) gfz = *gfp;
@@ -3254,15 +3299,15 @@ static int hist_build_launch(const uint8_t* codes, int64_t npad, const float* g,
 #define LAUNCH_HBK(NB, R, M, RT, C)                                                                           \
   hipLaunchKernelGGL((hist_build_kernel<NB, R, M, RT, C>), dim3(grid), dim3(threads), lds, stream, codes, npad, \
                      g, s2, nid, lk, ctl, nvb, qscale, (uint32_t)salt, F, fg, n_groups, wgpg, slot_lo, slot_cnt,  \
-                     slot16, pk_buf, partials, pp, ctl_prev, nid_out, writer, gfz, lpz)
+                     slot16, pk_buf, partials, pp, ctl_prev, nid_out, writer, gfz, lpz, joint, plane_src)
 #define LAUNCH_HBKC(NB, R, M, CP)                                                                                \
   hipLaunchKernelGGL((hist_build_kernel<NB, R, M, false, false, CP>), dim3(grid), dim3(threads), lds, stream, codes, \
                      npad, g, s2, nid, lk, ctl, nvb, qscale, (uint32_t)salt, F, fg, n_groups, wgpg, slot_lo,        \
-                     slot_cnt, slot16, pk_buf, partials, pp, ctl_prev, nid_out, writer, gfz, lpz)
+                     slot_cnt, slot16, pk_buf, partials, pp, ctl_prev, nid_out, writer, gfz, lpz, joint, plane_src)
 #define LAUNCH_HBK16(NB, M)                                                                                      \
   hipLaunchKernelGGL((hist_build_kernel<NB, 16, M, true, false, 1, true>), dim3(grid), dim3(threads), lds, stream, \
                      codes, npad, g, s2, nid, lk, ctl, nvb, qscale, (uint32_t)salt, F, fg, n_groups, wgpg, slot_lo,    \
-                     slot_cnt, slot16, pk_buf, partials, pp, ctl_prev, nid_out, writer, gfz, lpz)
+                     slot_cnt, slot16, pk_buf, partials, pp, ctl_prev, nid_out, writer, gfz, lpz, joint, plane_src)
 #define LAUNCH_HB(NB, R)                                            \
   do {                                                             \
     if (pkm == 0) LAUNCH_HBK(NB, R, 0, false, false);               \
@@ -3335,10 +3380,11 @@ H2OMX_API int h2omx_hist_build(const uint8_t* codes, int64_t npad, const float* 
                                const void* link, const int* ctl, const int* nvb, const double* qscale, int salt,
                                int F, int nbt, int fg, int n_groups, int wgpg, int slot_lo, int slot_cnt,
                                int rows_per_lane, int threads, const short* slot16, unsigned long long* pk_buf,
-                               int pkm, unsigned long long* partials, hipStream_t stream) {
+                               int pkm, unsigned long long* partials, const uint8_t* joint,
+                               const int* plane_src, hipStream_t stream) {
   return hist_build_launch(codes, npad, g, s2, nid, link, ctl, nvb, qscale, salt, F, nbt, fg, n_groups, wgpg, slot_lo,
                            slot_cnt, rows_per_lane, threads, slot16, pk_buf, pkm, partials, nullptr, nullptr, nullptr,
-                           0, stream);
+                           0, stream, nullptr, nullptr, joint, plane_src);
 }
 
 // Level 0 with the gradient pass fused in (PKM 5, see GradFuse): F / y / the
@@ -3348,7 +3394,8 @@ H2OMX_API int h2omx_hist_build_grad(const uint8_t* codes, int64_t npad, const in
                                     int slot_cnt, int rows_per_lane, int threads, unsigned long long* pk_buf,
                                     unsigned long long* partials, float* Fm, const float* y, const int* nid_leaf,
                                     const void* tree, int cap, float* g, float* h, int apply, int s_is_h,
-                                    int pk64, const void* gparams, hipStream_t stream) {
+                                    int pk64, const void* gparams, const uint8_t* joint, const int* plane_src,
+                                    hipStream_t stream) {
   if (gparams == nullptr) return kBadArg;
   GradFuse gf{};
   gf.F = Fm; gf.y = y; gf.nid = nid_leaf; gf.tree = reinterpret_cast<const TreeNode*>(tree);
@@ -3356,7 +3403,7 @@ H2OMX_API int h2omx_hist_build_grad(const uint8_t* codes, int64_t npad, const in
   gf.gp = *reinterpret_cast<const GradParams*>(gparams);
   return hist_build_launch(codes, npad, nullptr, nullptr, nullptr, nullptr, ctl, nvb, qscale, salt, F, nbt, fg,
                            n_groups, wgpg, 0, slot_cnt, rows_per_lane, threads, nullptr, pk_buf, 5, partials, nullptr,
-                           nullptr, nullptr, 0, stream, &gf);
+                           nullptr, nullptr, 0, stream, &gf, nullptr, joint, plane_src);
 }
 
 // Deeper level with the previous level's partition fused in (see ROUTE):
@@ -3366,11 +3413,11 @@ H2OMX_API int h2omx_hist_build_route(const uint8_t* codes, int64_t npad, const i
                                      const double* qscale, int F, int nbt, int fg, int n_groups, int wgpg,
                                      int slot_lo, int slot_cnt, int rows_per_lane, int threads,
                                      unsigned long long* pk_buf, int pkm, unsigned long long* partials,
-                                     hipStream_t stream) {
+                                     const uint8_t* joint, const int* plane_src, hipStream_t stream) {
   if (part_prev == nullptr) return kBadArg;
   return hist_build_launch(codes, npad, nullptr, nullptr, nid_prev, nullptr, ctl, nvb, qscale, 0, F, nbt, fg, n_groups,
                            wgpg, slot_lo, slot_cnt, rows_per_lane, threads, nullptr, pk_buf, pkm, partials, part_prev,
-                           ctl_prev, nid_out, writer, stream);
+                           ctl_prev, nid_out, writer, stream, nullptr, nullptr, joint, plane_src);
 }
 
 // h2omx_hist_build_route that also finalises the previous level (level
@@ -3384,12 +3431,13 @@ H2OMX_API int h2omx_hist_build_route_fin(const uint8_t* codes, int64_t npad, con
                                          const double* qscale, int F, int nbt, int fg, int n_groups, int wgpg,
                                          int slot_cnt, int rows_per_lane, int threads, unsigned long long* pk_buf,
                                          int pkm, unsigned long long* partials, const void* fbest, const void* params,
-                                         const void* level_out, int max_nodes, hipStream_t stream) {
+                                         const void* level_out, int max_nodes, const uint8_t* joint,
+                                         const int* plane_src, hipStream_t stream) {
   LevelPro lp{};
   if (!make_pro(lp, fbest, params, level_out, max_nodes)) return kBadArg;
   return hist_build_launch(codes, npad, nullptr, nullptr, nid_prev, nullptr, ctl, nvb, qscale, 0, F, nbt, fg, n_groups,
                            wgpg, 0, slot_cnt, rows_per_lane, threads, nullptr, pk_buf, pkm, partials, part_prev,
-                           ctl_prev, nid_out, 1, stream, nullptr, &lp);
+                           ctl_prev, nid_out, 1, stream, nullptr, &lp, joint, plane_src);
 }
 
 H2OMX_API int h2omx_hist_reduce(const unsigned long long* partials, int n_groups, int wgpg, int fg, int F, int nbt,
@@ -3429,7 +3477,8 @@ H2OMX_API int h2omx_split_find(const long long* built, const long long* parent_f
 static int reduce_split_launch(const unsigned long long* partials, int wgpg, int fg, int slot_lo, int slot_cnt,
                                const long long* parent_full, long long* full, const int* ctl, const void* link,
                                const int* nvb, const uint8_t* tree_fmask, const double* qscale, const void* params,
-                               int nbt, void* out, hipStream_t stream, const LevelFin* finp = nullptr) {
+                               int nbt, void* out, hipStream_t stream, const LevelFin* finp = nullptr,
+                               const int* feat_plane = nullptr) {
   const SplitParams p = *reinterpret_cast<const SplitParams*>(params);
   if (slot_cnt < 1 || wgpg < 1 || fg < 1 || p.F < 1) return kBadArg;
   const NodeLink* lk = reinterpret_cast<const NodeLink*>(link);
@@ -3439,7 +3488,7 @@ static int reduce_split_launch(const unsigned long long* partials, int wgpg, int
   if (finp) fin = *finp;
 #define LAUNCH_RSK(NB, CAT, FIN)                                                                                \
   hipLaunchKernelGGL((reduce_split_kernel<NB, CAT, FIN>), grid, dim3(1024), 0, stream, partials, wgpg, fg, slot_lo, \
-                     slot_cnt, parent_full, full, ctl, lk, nvb, tree_fmask, qscale, p, o, fin)
+                     slot_cnt, parent_full, full, ctl, lk, nvb, tree_fmask, qscale, p, o, fin, feat_plane)
 #define LAUNCH_RS(NB)                                           \
   do {                                                          \
     if (p.catf != nullptr && finp) LAUNCH_RSK(NB, true, true);  \
@@ -3462,9 +3511,9 @@ static int reduce_split_launch(const unsigned long long* partials, int wgpg, int
 H2OMX_API int h2omx_reduce_split(const unsigned long long* partials, int wgpg, int fg, int slot_lo, int slot_cnt,
                                  const long long* parent_full, long long* full, const int* ctl, const void* link,
                                  const int* nvb, const uint8_t* tree_fmask, const double* qscale, const void* params,
-                                 int nbt, void* out, hipStream_t stream) {
+                                 int nbt, void* out, const int* feat_plane, hipStream_t stream) {
   return reduce_split_launch(partials, wgpg, fg, slot_lo, slot_cnt, parent_full, full, ctl, link, nvb, tree_fmask,
-                             qscale, params, nbt, out, stream);
+                             qscale, params, nbt, out, stream, nullptr, feat_plane);
 }
 
 // One-pass level (slot_lo = 0, slot_cnt = the level's slots) with the level
@@ -3475,12 +3524,12 @@ H2OMX_API int h2omx_reduce_split_fin(const unsigned long long* partials, int wgp
                                      const long long* parent_full, long long* full, const int* ctl, const void* link,
                                      const int* nvb, const uint8_t* tree_fmask, const double* qscale,
                                      const void* params, int nbt, void* out, const void* level_out, int* ticket,
-                                     hipStream_t stream) {
+                                     const int* feat_plane, hipStream_t stream) {
   LevelFin fin{};
   if (!copy_level_out(fin.lv, level_out) || ticket == nullptr) return kBadArg;
   fin.ticket = ticket;
   return reduce_split_launch(partials, wgpg, fg, 0, slot_cnt, parent_full, full, ctl, link, nvb, tree_fmask, qscale,
-                             params, nbt, out, stream, &fin);
+                             params, nbt, out, stream, &fin, feat_plane);
 }
 
 // N-rank fused level (reduce_split_p2p_kernel); desc = host P2PDesc image.
@@ -6030,6 +6079,57 @@ H2OMX_API int h2omx_codes_rowmajor(const uint8_t* codes, long long npad, int F, 
   const int64_t nb = (n + RM_ROWS - 1) / RM_ROWS;
   hipLaunchKernelGGL(codes_rowmajor_kernel, dim3((unsigned)nb), dim3(256), 0, stream, codes, (int64_t)npad, F,
                      (int64_t)n, rm, fp);
+  return launch_status();
+}
+
+// Joint code plane of one bundle of k low-cardinality features (binning.py
+// plan_bundles): out[r] = sum of digit_j(r) * stride_j over the members, digit
+// = the feature's bin, its NA code nbt - 1 -> its valid-bin count (the mixed
+// radix's last digit).  members: int[k][3] = (feature, valid bins, stride), the
+// product of the radices (valid bins + 1) <= nbt, so every joint code < nbt.
+// Padding rows (>= n) get code 0.  One lane: 16 consecutive rows.
+__global__ __launch_bounds__(256) void bundle_planes_kernel(const uint8_t* __restrict__ codes, int64_t npad, int64_t n,
+                                                            int nbt, const int* __restrict__ members, int k,
+                                                            uint8_t* __restrict__ out) {
+  const int64_t r0 = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * 16;
+  if (r0 >= npad) return;
+  uint32_t acc[16];
+#pragma unroll
+  for (int i = 0; i < 16; ++i) acc[i] = 0u;
+  for (int j = 0; j < k; ++j) {
+    const int f = members[3 * j], nv = members[3 * j + 1], stride = members[3 * j + 2];
+    const uint4 c4 = *reinterpret_cast<const uint4*>(codes + (int64_t)f * npad + r0);
+    const uint32_t cw[4] = {c4.x, c4.y, c4.z, c4.w};
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+      const int c = (cw[i >> 2] >> (8 * (i & 3))) & 0xff;
+      const int digit = c == nbt - 1 ? nv : min(c, nv - 1);
+      acc[i] += (uint32_t)(digit * stride);
+    }
+  }
+  uint32_t ow[4];
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    ow[q] = 0u;
+#pragma unroll
+    for (int b = 0; b < 4; ++b) {
+      const int i = 4 * q + b;
+      ow[q] |= (r0 + i < n ? (acc[i] & 0xffu) : 0u) << (8 * b);
+    }
+  }
+  *reinterpret_cast<uint4*>(out + r0) = make_uint4(ow[0], ow[1], ow[2], ow[3]);
+}
+
+// BinnedMatrix.bundle: one joint plane (out [npad], 16-byte aligned) from codes
+// [F][npad] (npad % 64 == 0); members on the device
+H2OMX_API int h2omx_bundle_plane(const uint8_t* codes, long long npad, long long n, int nbt, const int* members,
+                                 int k, uint8_t* out, hipStream_t stream) {
+  if (!codes || !members || !out || k < 2 || k > 8 || nbt < 4 || nbt > 256 || npad < 64 || npad % 64 || n < 0 ||
+      n > npad || (reinterpret_cast<uintptr_t>(out) & 15) || (reinterpret_cast<uintptr_t>(codes) & 15))
+    return kBadArg;
+  const int64_t lanes = npad / 16;
+  hipLaunchKernelGGL(bundle_planes_kernel, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, stream, codes,
+                     (int64_t)npad, (int64_t)n, nbt, members, k, out);
   return launch_status();
 }
 

@@ -21,6 +21,94 @@ ROW_ALIGN = 64
 
 
 @dataclass
+class BundlePlan:
+    """Histogram planes of a binned matrix whose low-cardinality features share
+    joint code planes (:func:`plan_bundles`).
+
+    A bundle of features with radices ``r_k = nvb_k + 1`` (one digit per valid
+    bin + one for NA) and ``prod r_k <= nbt`` gets ONE plane holding the mixed
+    radix code ``sum digit_k * stride_k``; the digit is the feature's bin code,
+    its NA code ``nbt - 1`` mapped to ``nvb_k``.  A histogram of int64 sums
+    over the joint code, summed over the other digits, IS the feature's own
+    histogram (integer adds commute; the per-row quantised values do not depend
+    on the plane), so every split scan sees exactly the rows it saw before."""
+    nbt: int
+    bundles: list            # per bundle: [(feature, nvb, stride), ...] in digit order
+    plane_src: np.ndarray    # int32 [P]: >= 0 the feature whose own plane this is, < 0: joint plane ~src
+    plane_nvb: np.ndarray    # int32 [P]: valid bins per plane (joint planes: nbt - 1, a full-width slice)
+    feat_plane: np.ndarray   # int32 [F][3]: (plane position, stride, radix); radix 0 = its own plane
+    # device copies (BinnedMatrix.bundle)
+    joint: torch.Tensor | None = None          # uint8 [n_bundles][npad]
+    plane_src_dev: torch.Tensor | None = None
+    plane_nvb_dev: torch.Tensor | None = None
+    feat_plane_dev: torch.Tensor | None = None
+
+    @property
+    def P(self) -> int:
+        return int(self.plane_src.size)
+
+    def encode(self, codes: np.ndarray) -> np.ndarray:
+        """Joint planes uint8 [n_bundles][n] of feature-major ``codes`` [F][n]
+        (NumPy image of bundle_planes_kernel)."""
+        out = np.zeros((len(self.bundles), codes.shape[1]), np.int64)
+        for b, members in enumerate(self.bundles):
+            for f, nv, stride in members:
+                c = codes[f].astype(np.int64)
+                out[b] += np.where(c == self.nbt - 1, nv, np.minimum(c, nv - 1)) * stride
+        return out.astype(np.uint8)
+
+    def marginal(self, joint_hist: np.ndarray, f: int) -> np.ndarray:
+        """Feature ``f``'s histogram [nbt] from its bundle's joint histogram
+        [nbt] (NumPy image of reduce_split's rs_marginalise)."""
+        _, stride, radix = (int(v) for v in self.feat_plane[f])
+        digit = (np.arange(self.nbt) // stride) % radix
+        bins = np.where(digit == radix - 1, self.nbt - 1, digit)
+        out = np.zeros(self.nbt, joint_hist.dtype)
+        np.add.at(out, bins, joint_hist)
+        return out
+
+
+def plan_bundles(nvb, nbt: int) -> BundlePlan | None:
+    """Group low-cardinality features into joint code planes.  Candidates:
+    radix ``nvb + 1 <= nbt / 2``; first fit in (radix, feature) order with the
+    product of a bundle's radices <= nbt; bundles of one feature are dropped.
+    Planes keep feature order, a joint plane standing where its lowest-numbered
+    member stood.  None: nothing to bundle."""
+    nvb = [int(v) for v in np.asarray(nvb).reshape(-1)]
+    F = len(nvb)
+    open_b: list[tuple[list, int]] = []     # (members, product)
+    for radix, f in sorted((nvb[f] + 1, f) for f in range(F) if nvb[f] >= 1 and nvb[f] + 1 <= nbt // 2):
+        for i, (members, prod) in enumerate(open_b):
+            if prod * radix <= nbt:
+                members.append((f, radix - 1, prod))
+                open_b[i] = (members, prod * radix)
+                break
+        else:
+            open_b.append(([(f, radix - 1, 1)], radix))
+    bundles = [m for m, _ in open_b if len(m) >= 2]
+    if not bundles:
+        return None
+    of = {f: b for b, m in enumerate(bundles) for f, _, _ in m}
+    feat_plane = np.zeros((F, 3), np.int32)
+    src, pnvb, pos_of = [], [], {}
+    for f in range(F):
+        b = of.get(f)
+        if b is None:
+            feat_plane[f, 0] = len(src)
+            src.append(f)
+            pnvb.append(nvb[f])
+        elif b not in pos_of:
+            pos_of[b] = len(src)
+            src.append(~b)
+            pnvb.append(nbt - 1)
+    for b, members in enumerate(bundles):
+        for f, nv, stride in members:
+            feat_plane[f] = (pos_of[b], stride, nv + 1)
+    return BundlePlan(nbt=nbt, bundles=bundles, plane_src=np.asarray(src, np.int32),
+                      plane_nvb=np.asarray(pnvb, np.int32), feat_plane=feat_plane)
+
+
+@dataclass
 class BinnedMatrix:
     codes: torch.Tensor      # uint8 [F][npad]
     edges: torch.Tensor      # float32 [F][nbt]  (edges[f][:nvb[f]-1] used)
@@ -94,6 +182,35 @@ class BinnedMatrix:
                 rm[:, : self.F] = c[:, : self.n].t()
             self._codes_rm = rm
         return self._codes_rm
+
+    _bundle: object = None
+
+    @property
+    def bundle(self) -> BundlePlan | None:
+        """The joint code planes of the low-cardinality features (built once
+        per matrix: the codes are fixed for a fit) with their plane tables on
+        the device, None when no two features fit one plane.  ``codes`` and
+        every per-feature consumer stay as they are; only the histogram
+        kernel of the one-rank scan engine reads the joint planes."""
+        if self._bundle is None:
+            plan = plan_bundles(self.nvb.cpu().numpy(), self.nbt)
+            c = self.codes
+            if plan is None or not (c.is_cuda and c.is_contiguous() and c.shape == (self.F, self.npad)
+                                    and self.npad % 64 == 0):
+                self._bundle = False
+            else:
+                dev = c.device
+                plan.joint = torch.empty((len(plan.bundles), self.npad), dtype=torch.uint8, device=dev)
+                lib = ops.tree_lib()
+                for b, members in enumerate(plan.bundles):
+                    m_t = torch.tensor(members, dtype=torch.int32, device=dev)
+                    ops.check(lib.h2omx_bundle_plane(ops.P(c), self.npad, self.n, self.nbt, ops.P(m_t), len(members),
+                                                     ops.P(plan.joint[b]), ops.stream(dev)), "bundle_plane")
+                plan.plane_src_dev = torch.from_numpy(plan.plane_src).to(dev)
+                plan.plane_nvb_dev = torch.from_numpy(plan.plane_nvb).to(dev)
+                plan.feat_plane_dev = torch.from_numpy(plan.feat_plane).to(dev)
+                self._bundle = plan
+        return self._bundle or None
 
     def edges_numpy(self):
         e = self.edges.cpu().numpy()

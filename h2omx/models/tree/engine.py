@@ -144,6 +144,11 @@ class HipTreeBuilder:
     # level 0 with the gradient pass fused in (off: see can_fuse_grad), chained
     # tree_begin in graph replay
     FUSE_ROUTE = True
+    # one rank, scan engine: low-cardinality features share joint histogram planes
+    # (binning.BundlePlan: HIGGS 28 features -> 25 planes); reduce_split
+    # marginalises the joint rows, so the trees are bit-identical.  N-rank levels
+    # and the segmented engine keep one plane per feature
+    BUNDLE = True
     PK32 = True
     FUSE_GRAD = False
     CHAIN_BEGIN = True
@@ -327,6 +332,21 @@ class HipTreeBuilder:
         # quantises with the SAME scale (derived from the global row count above), so
         # the summed int64 histograms are in one unit
         self.pk32 = self.max_rows_per_wg >= 65536 and self.PK32
+        # histogram planes (BUNDLE): set only now, so max_rows_per_wg above comes from
+        # the plans on F planes - the scales equal an N-rank run's on the same rows -
+        # and the plans on fewer planes are held to chunks <= that bound (see _plan)
+        self.planes = None
+        if self.BUNDLE and not self.segmented and (comm is None or comm.world_size <= 1):
+            self.planes = bm.bundle
+        self.n_planes = self.planes.P if self.planes is not None else self.F
+
+    def _hist_planes(self):
+        """hist_build's (planes, valid bins per plane, joint planes, plane table) and
+        reduce_split's feature -> plane table"""
+        pl = self.planes
+        if pl is None:
+            return self.F, self.bm.nvb, None, None, None
+        return pl.P, pl.plane_nvb_dev, pl.joint, pl.plane_src_dev, pl.feat_plane_dev
 
     # -- buffers -----------------------------------------------------------
     def _ticket_buf(self, numel: int) -> torch.Tensor:
@@ -394,7 +414,9 @@ class HipTreeBuilder:
 
     def _plan(self, max_slots: int, budget: int, threads: int, units: int | None = None, mult: int = 1):
         per_slot_feat = self.nbt * 8 * mult
-        F = self.F
+        # the kernel's "features" are histogram planes (a builder without a plane
+        # count - before __init__ set it, or none at all - plans one per feature)
+        F = getattr(self, "n_planes", None) or self.F
         if max_slots * per_slot_feat <= budget:
             slot_cnt = max_slots
             fg_max = max(1, min(F, 256, budget // (max_slots * per_slot_feat)))
@@ -533,6 +555,7 @@ class HipTreeBuilder:
         st = ops.stream(self.dev)
         P = ops.P
         F, nbt = self.F, self.nbt
+        Fh, nvb_h, joint, plane_src, feat_plane = self._hist_planes()
         spp = self._params(tree_index)
         sp = self._sp
         comm = self.comm if (self.comm is not None and self.comm.world_size > 1) else None
@@ -645,12 +668,13 @@ class HipTreeBuilder:
                     ops.check(lib.h2omx_reduce_split_fin(P(partials), wgpg, fg, slot_cnt, P(full_prev), P(full_cur),
                                                          P(ctl_cur), P(link[cur]), P(bm.nvb), P(tree_fmask),
                                                          P(self.qscale), spp, nbt, P(fbest), ctypes.addressof(lvo),
-                                                         P(self._fin_ticket), st),
+                                                         P(self._fin_ticket), P(feat_plane), st),
                               "reduce_split_fin")
                 elif rs:
                     ops.check(lib.h2omx_reduce_split(P(partials), wgpg, fg, slot_lo, slot_cnt, P(full_prev),
                                                      P(full_cur), P(ctl_cur), P(link[cur]), P(bm.nvb),
-                                                     P(tree_fmask), P(self.qscale), spp, nbt, P(fbest), st),
+                                                     P(tree_fmask), P(self.qscale), spp, nbt, P(fbest),
+                                                     P(feat_plane), st),
                               "reduce_split")
                 else:
                     ops.check(lib.h2omx_hist_reduce(P(partials), n_groups, wgpg, fg, F, nbt, slot_lo, slot_cnt,
@@ -666,10 +690,11 @@ class HipTreeBuilder:
                         # level d - 1 is finalised AND routed in here: nid_buf[d - 1] -> nid_buf[d]
                         ops.check(lib.h2omx_hist_build_route_fin(
                             P(bm.codes), bm.npad, P(None if (d == 1 and self.implicit_root) else nid_buf[(d - 1) % 2]),
-                            P(part_prev), P(ctl_nxt), P(nid_buf[d % 2]), P(ctl_cur), P(bm.nvb), P(self.qscale),
-                            F, nbt, plan["fg"], plan["n_groups"], plan["wgpg"], plan["slot_cnt"],
+                            P(part_prev), P(ctl_nxt), P(nid_buf[d % 2]), P(ctl_cur), P(nvb_h), P(self.qscale),
+                            Fh, nbt, plan["fg"], plan["n_groups"], plan["wgpg"], plan["slot_cnt"],
                             self.ROWS_PER_LANE, plan["threads"], P(self.pk),
-                            (4 if self.pk32 else 2) + (64 if nid16 else 0), P(partials), *pend["args"], st),
+                            (4 if self.pk32 else 2) + (64 if nid16 else 0), P(partials), *pend["args"],
+                            P(joint), P(plane_src), st),
                             "hist_build_route_fin")
                         pend = None
                     elif d > 0 and fuse and self._fused_level(d):
@@ -677,20 +702,21 @@ class HipTreeBuilder:
                         ops.check(lib.h2omx_hist_build_route(
                             P(bm.codes), bm.npad, P(None if (d == 1 and self.implicit_root) else nid_buf[(d - 1) % 2]),
                             P(part_prev), P(ctl_nxt),
-                            P(nid_buf[d % 2]), 1 if ps == 0 else 0, P(ctl_cur), P(bm.nvb), P(self.qscale), F, nbt,
+                            P(nid_buf[d % 2]), 1 if ps == 0 else 0, P(ctl_cur), P(nvb_h), P(self.qscale), Fh, nbt,
                             plan["fg"], plan["n_groups"], plan["wgpg"], slot_lo, plan["slot_cnt"],
                             self.ROWS_PER_LANE, plan["threads"], P(self.pk),
                             (4 if self.pk32 else 2) + (64 if nid16 else 0),
-                            P(partials), st),
+                            P(partials), P(joint), P(plane_src), st),
                             "hist_build_route")
                     elif d == 0 and grad_fuse is not None:
                         gf = grad_fuse
                         ops.check(lib.h2omx_hist_build_grad(
-                            P(bm.codes), bm.npad, P(ctl_cur), P(bm.nvb), P(self.qscale), tree_index & 0x7FFFFFFF,
-                            F, nbt, plan["fg"], plan["n_groups"], plan["wgpg"], plan["slot_cnt"],
+                            P(bm.codes), bm.npad, P(ctl_cur), P(nvb_h), P(self.qscale), tree_index & 0x7FFFFFFF,
+                            Fh, nbt, plan["fg"], plan["n_groups"], plan["wgpg"], plan["slot_cnt"],
                             self.ROWS_PER_LANE, plan["threads"], P(self.pk), P(partials), P(gf["F"]), P(gf["y"]),
                             P(self.nid), P(self.tree_buf), self.capacity, P(g), P(h), 1 if gf["apply"] else 0,
-                            0 if p.mode == 0 else 1, 0 if self.pk32 else 1, ctypes.addressof(gf["gp"]), st),
+                            0 if p.mode == 0 else 1, 0 if self.pk32 else 1, ctypes.addressof(gf["gp"]),
+                            P(joint), P(plane_src), st),
                             "hist_build_grad")
                     else:
                         # level 0 stores the packed quantised rows; deeper levels read them
@@ -698,14 +724,14 @@ class HipTreeBuilder:
                         ops.check(lib.h2omx_hist_build(
                             P(bm.codes), bm.npad, P(g), P(s2),
                             P(None if (d == 0 and self.implicit_root) else (nid_buf[d % 2] if fuse else self.nid)),
-                            P(link[cur]), P(ctl_cur), P(bm.nvb),
-                            P(self.qscale), tree_index & 0x7FFFFFFF, F, nbt, plan["fg"], plan["n_groups"],
+                            P(link[cur]), P(ctl_cur), P(nvb_h),
+                            P(self.qscale), tree_index & 0x7FFFFFFF, Fh, nbt, plan["fg"], plan["n_groups"],
                             plan["wgpg"], slot_lo, plan["slot_cnt"], self.ROWS_PER_LANE, plan["threads"],
                             P(self.slot16), P(self.pk),
                             ((6 if pk_boost else 1 + (2 if self.pk32 else 0)) if d == 0
                              else 2 + (2 if self.pk32 else 0))
                             + ({8: 16, 4: 32}.get(self.L0_COPIES, 0) if l0_copies else 0),
-                            P(partials), st),
+                            P(partials), P(joint), P(plane_src), st),
                             "hist_build")
                 with T("hist_reduce"):
                     reduce(plan["n_groups"], plan["wgpg"], plan["fg"], slot_lo, plan["slot_cnt"])
@@ -1131,7 +1157,7 @@ class HipTreeBuilder:
                                                    P(ctl_cur), P(bm.nvb), P(self.qscale), tree_index & 0x7FFFFFFF,
                                                    F, nbt, plan["fg"], plan["n_groups"], plan["wgpg"], slot_lo,
                                                    plan["slot_cnt"], self.ROWS_PER_LANE, plan["threads"],
-                                                   None, None, 0, P(partials), st), "hist_build")
+                                                   None, None, 0, P(partials), None, None, st), "hist_build")
                     ops.check(lib.h2omx_hist_reduce(P(partials), plan["n_groups"], plan["wgpg"], plan["fg"], F, nbt,
                                                     slot_lo, plan["slot_cnt"], P(ctl_cur), P(built), st),
                               "hist_reduce")

@@ -18,14 +18,16 @@ _CT = {"P": ctypes.c_void_p, "I": ctypes.c_int, "L": ctypes.c_int64, "F": ctypes
 TREE_SIGS = {
     "h2omx_tree_sizes": "P",
     "h2omx_bin_features": "PLLIPPIPLS",
-    "h2omx_hist_build": "PLPPPPPPPIIIIIIIIIIPPIPS",
+    # histogram planes (+ joint, plane_src; reduce_split: + feat_plane): null = one plane per feature
+    "h2omx_hist_build": "PLPPPPPPPIIIIIIIIIIPPIPPPS",
     "h2omx_hist_reduce": "PIIIIIIIPPS",
-    "h2omx_hist_build_route": "PLPPPPIPPPIIIIIIIIIPIPS",
-    "h2omx_hist_build_grad": "PLPPPIIIIIIIIIPPPPPPIPPIIIPS",
+    "h2omx_hist_build_route": "PLPPPPIPPPIIIIIIIIIPIPPPS",
+    "h2omx_hist_build_grad": "PLPPPIIIIIIIIIPPPPPPIPPIIIPPPS",
     "h2omx_split_find": "PPPPPPPPPIIPS",
-    "h2omx_reduce_split": "PIIIIPPPPPPPPIPS",
+    "h2omx_reduce_split": "PIIIIPPPPPPPPIPPS",
     "h2omx_reduce_split_p2p": "PPIIIPPPPPPPPIIPS",
-    "h2omx_reduce_split_fin": "PIIIPPPPPPPPIPPPS",
+    "h2omx_reduce_split_fin": "PIIIPPPPPPPPIPPPPS",
+    "h2omx_bundle_plane": "PLLIPIPS",
     "h2omx_node_best_finalize_p2p": "PPPIPS",
     "h2omx_leaf_finalize_p2p": "PPPPPPIIPIIPPLPS",
     "h2omx_level_finalize": "PPPIPIPS",
@@ -34,7 +36,7 @@ TREE_SIGS = {
     "h2omx_partition_final": "PLPPPIPPPPIPPPIPPPIPS",
     "h2omx_partition_route": "PLPPPIPPIPIS",
     # level finalisation as the consumer launch's prologue (+ fbest, params, level_out, max_nodes)
-    "h2omx_hist_build_route_fin": "PLPPPPPPPIIIIIIIIPIPPPPIS",
+    "h2omx_hist_build_route_fin": "PLPPPPPPPIIIIIIIIPIPPPPIPPS",
     "h2omx_partition_route_fin": "PLPPPIPPIPIPPPIS",
     "h2omx_partition_final_fin": "PLPPPIPPPPIPPPIPPPIPPPPIS",
     "h2omx_leaf_reduce": "PIIPS",
