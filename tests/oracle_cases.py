@@ -18,6 +18,16 @@ def _mixed(n, F, seed, task):
         y = (rng.random(n) < 1 / (1 + np.exp(-logit))).astype(np.float32)
     elif task == "reg":
         y = (logit + rng.normal(size=n)).astype(np.float32)
+    elif task in ("count", "pos", "zpos"):
+        mu = np.exp(np.clip(0.4 * logit, -3, 3))
+        if task == "count":
+            y = rng.poisson(mu).astype(np.float32)
+        else:
+            y = rng.gamma(2, mu / 2).astype(np.float32)
+            if task == "zpos":
+                y[rng.random(n) < 0.3] = 0.0
+    elif task == "heavy":
+        y = (logit + rng.standard_t(3, n)).astype(np.float32)
     else:
         y = np.digitize(logit, [-0.5, 1.5]).astype(np.float32)
     return X, y
@@ -37,10 +47,17 @@ DATA = {
     "big": lambda: _mixed(N_PK32, 9, 23, "bin"),
     "multi": lambda: _mixed(N, 7, 24, "multi"),
     "drf": lambda: _mixed(N, 7, 25, "bin"),
+    "count": lambda: _mixed(N, 7, 31, "count"),
+    "pos": lambda: _mixed(N, 7, 32, "pos"),
+    "zpos": lambda: _mixed(N, 7, 33, "zpos"),
+    "heavy_laplace": lambda: _mixed(N, 7, 34, "heavy"),
+    "heavy_quantile": lambda: _mixed(N, 7, 35, "heavy"),
+    "heavy_huber": lambda: _mixed(N, 7, 36, "heavy"),
 }
 
-# name -> data set, nbins, train_ensemble arguments, TreeParams arguments, engine
-# ("scan" / "seg"), HipTreeBuilder class attributes to set
+# name -> data set, nbins, train_ensemble arguments (wobs: seed of the observation
+# weights, see case_weights), TreeParams arguments, engine ("scan" / "seg"),
+# HipTreeBuilder class attributes to set
 CASES = {
     "scan_defaults": dict(
         data="fill256", nbins=255, dist="bernoulli", ntrees=3, engine="scan",
@@ -70,6 +87,23 @@ for _name, _wave in (("seg_drf_direct_wg", 0), ("seg_drf_direct_wave", 1 << 30))
     CASES[_name] = dict(CASES["seg_drf"],
                         attrs=dict(BAG_COMPACT=True, DIRECT_MIN_NODES=2, DIRECT_WAVE_ROWS=_wave))
 
+# the gradient passes of the remaining distributions (tests/gradref.py closes the
+# chain data -> gradients -> tree -> margins), with observation weights and a bag
+_GRAD = dict(ntrees=3, engine="scan", attrs={})
+CASES.update({
+    "poisson_w": dict(_GRAD, data="count", nbins=63, dist="poisson", wobs=77,
+                      tp=dict(max_depth=5, min_rows=10, learn_rate=0.3)),
+    "gamma": dict(_GRAD, data="pos", nbins=255, dist="gamma", tp=dict(max_depth=4, min_rows=10, learn_rate=0.3)),
+    "tweedie": dict(_GRAD, data="zpos", nbins=255, dist="tweedie", dist_kw=dict(tweedie_power=1.2),
+                    tp=dict(max_depth=4, min_rows=10, learn_rate=0.3)),
+    "laplace": dict(_GRAD, data="heavy_laplace", nbins=63, dist="laplace",
+                    tp=dict(max_depth=5, min_rows=10, learn_rate=0.3)),
+    "quantile_bag": dict(_GRAD, data="heavy_quantile", nbins=255, dist="quantile", dist_kw=dict(quantile_alpha=0.3),
+                         sample_rate=0.7, tp=dict(max_depth=5, min_rows=10, learn_rate=0.3)),
+    "huber_w": dict(_GRAD, data="heavy_huber", nbins=255, dist="huber", dist_kw=dict(huber_delta=0.8), wobs=77,
+                    tp=dict(max_depth=5, min_rows=10, learn_rate=0.3)),
+})
+
 _cache = {}
 
 
@@ -90,6 +124,15 @@ def case_data(name):
             a.setflags(write=False)
         _cache[key] = (X, y, e, nv, nbt, codes)
     return _cache[key]
+
+
+def case_weights(name):
+    """observation weights of a case (float32, uniform in [0.5, 2)), or None"""
+    c = CASES[name]
+    if "wobs" not in c:
+        return None
+    n = case_data(name)[0].shape[1]
+    return np.random.default_rng(c["wobs"]).uniform(0.5, 2, n).astype(np.float32)
 
 
 def tree_params(name):

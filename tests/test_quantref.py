@@ -10,7 +10,7 @@ import pytest
 import torch
 
 import quantref as Q
-from oracle_cases import CASES, builder_class, case_data, tree_params
+from oracle_cases import CASES, builder_class, case_data, case_weights, tree_params
 from h2omx.models.tree import TreeParams, bin_matrix, compute_edges
 from h2omx.reference.tree import RefTreeBuilder, bag_weights, dist_grad
 from treecmp import reachable
@@ -209,7 +209,8 @@ def cpu_boost(name, trees_out=None):
     """The case's boosting run with the oracle as the tree builder (float64
     gradients from the reference; the audit counts near-ties, it does not
     compare with the GPU): near-tie nodes per tree."""
-    from h2omx.models.tree.boost import _tree_fmask, init_margin
+    from h2omx.models.tree.boost import _tree_fmask, init_margin, weighted_quantile
+    from h2omx.models.tree.engine import GRAD_BOUNDS
 
     c = CASES[name]
     X, y, e, nv, nbt, codes = case_data(name)
@@ -217,22 +218,31 @@ def cpu_boost(name, trees_out=None):
     p = tree_params(name)
     dist, K = c["dist"], (c.get("nclass", 1) if c["dist"] == "multinomial" else 1)
     rate, seed = c.get("sample_rate", 1.0), 3
+    wobs, dist_kw = case_weights(name), c.get("dist_kw", {})
     m = Q.host_max_rows_per_wg(n, F, nbt, segmented=c["engine"] == "seg", cls=builder_class(name))
-    Fm = np.repeat(init_margin(dist, y, None, K)[:, None], n, 1).astype(np.float32)
-    fixed = K == 1 and dist == "bernoulli"
+    if dist in ("laplace", "quantile"):
+        q = 0.5 if dist == "laplace" else dist_kw.get("quantile_alpha", 0.5)
+        init = np.array([weighted_quantile(y, None if wobs is None else torch.from_numpy(wobs), q)])
+    else:
+        init = init_margin(dist, y, wobs, K)
+    Fm = np.repeat(init[:, None], n, 1).astype(np.float32)
+    # bounded gradients of unweighted rows quantise with the bound scales (GpuBooster._bounds)
+    fixed = K == 1 and wobs is None and dist in GRAD_BOUNDS
     counts = []
     for t in range(c["ntrees"]):
         wb = bag_weights(n, rate, seed, t)
+        if wobs is not None:
+            wb = wobs * wb
         if K == 1:
-            grads = [dist_grad(dist, Fm[0], y)]
+            grads = [dist_grad(dist, Fm[0], y, **dist_kw)]
         else:
             z = np.exp(Fm - Fm.max(axis=0, keepdims=True))
             pr = z / z.sum(axis=0, keepdims=True)
             grads = [(pr[k] - (y == k), np.maximum(pr[k] * (1 - pr[k]), 1e-16)) for k in range(K)]
         for k in range(K):
             g, h = ((v * wb).astype(np.float32) for v in grads[k])
-            w = wb if rate < 1.0 else None
-            mx = (1.0, 0.25, 1.0) if fixed else (np.abs(g).max(), h.max(), 1.0)
+            w = wb if (rate < 1.0 or wobs is not None) else None
+            mx = GRAD_BOUNDS[dist] if fixed else (np.abs(g).max(), h.max(), 1.0 if w is None else w.max())
             qs = Q.scales(np.array([*mx, 0.0], np.float32).view(np.int32), p.mode, m)
             tree, leaf, rec = Q.grow(codes, nv, e, g, h, w, p, qs, 0, t * K + k, _tree_fmask(p, F, t, None))
             Fm[k] += tree["value"][leaf]

@@ -362,7 +362,9 @@ def test_fused_gradient_level_matches_boost_update(cuda_dev, monkeypatch, n, mod
 @pytest.mark.parametrize("dist,depth,min_rows,n,ntrees", [("bernoulli", 5, 10, 400_000, 6),
                                                           ("gaussian", 7, 3, 150_000, 6),
                                                           ("bernoulli", 1, 3, 50_000, 6),
-                                                          ("bernoulli", 4, 3, 60_000, 70)])
+                                                          ("bernoulli", 4, 3, 60_000, 70),
+                                                          ("laplace", 4, 3, 60_000, 6),
+                                                          ("quantile", 5, 3, 60_001, 6)])
 def test_graph_replay_matches_eager(cuda_dev, monkeypatch, dist, depth, min_rows, n, ntrees):
     """Each boosting step replayed as one HIP graph (tree index / dither salt
     taken from the device counter) builds bit-identical trees and margins to
@@ -370,13 +372,16 @@ def test_graph_replay_matches_eager(cuda_dev, monkeypatch, dist, depth, min_rows
     chained step (next tree's begin inside the leaf finalisation, the tree
     archive inside boost_update); even depth puts the final control block in
     the level-0 slot the chained begin rewrites; 70 trees wrap the 64-slot
-    archive ring."""
+    archive ring.  Laplace and quantile (alpha 0.3) have fixed bounds too:
+    their chained steps re-derive (g, h) in the final partition through
+    dist_grad's sign and quantile branches."""
     from h2omx.models.tree import boost as B
 
     X, y = _data(n=n, F=11, seed=21, task="bin" if dist == "bernoulli" else "reg")
     _, bg = _both(X, y, 255)
     tp = TreeParams(max_depth=depth, min_rows=min_rows, learn_rate=0.2)
     yt = torch.from_numpy(y).cuda()
+    dist_kw = {"quantile_alpha": 0.3} if dist == "quantile" else None
     made = []
     init = B.GpuBooster.__init__
 
@@ -388,11 +393,11 @@ def test_graph_replay_matches_eager(cuda_dev, monkeypatch, dist, depth, min_rows
     out = {}
     for flag in ("0", "1"):
         monkeypatch.setenv("H2OMX_TREE_GRAPH", flag)
-        out[flag] = train_ensemble(bg, yt, dist=dist, ntrees=ntrees, tparams=tp, seed=5)
+        out[flag] = train_ensemble(bg, yt, dist=dist, ntrees=ntrees, tparams=tp, seed=5, dist_kw=dist_kw)
     assert not made[0].graph_used and made[1].graph_used, made[1].graph_error
     from h2omx.models.tree.engine import HipTreeBuilder as _HTB
 
-    if dist == "bernoulli" and _HTB.CHAIN_BEGIN:
+    if dist in ("bernoulli", "laplace", "quantile") and _HTB.CHAIN_BEGIN:
         assert made[1].graph_chain
     a, b = out["0"], out["1"]
     assert a.trees.shape == b.trees.shape
