@@ -3,18 +3,29 @@
 The reference is the same update computed by torch autograd in float64 on the
 CPU (forward, softmax cross-entropy / squared loss averaged over the batch,
 backward) followed by H2O's ADADELTA (``reference/dense.py adadelta_``).
-Both GPU paths of ``models/deeplearning._DLTrainer`` are pinned:
+The reference (``tests/dlref.py``) is whole-step autograd, which is only
+valid while no Rectifier pre-activation sits within fp32 rounding of zero, so
+the batches here are small (M <= 256).  At these sizes both GPU paths of
+``models/deeplearning._DLTrainer`` are pinned:
 
 * the fused small-batch chain (``ops/mlp.py`` / ``csrc/mlp_kernels.hip``:
   forward, loss gradient, backward and ADADELTA in 2 L - 1 launches);
 * the per-op path (GEMM kernels, fused activation backward, the bias /
-  output-layer gradient folds inside the ADADELTA kernel).
+  output-layer gradient folds inside the ADADELTA kernel); with M <= 256
+  ``ops/dense.py`` routes every product to the small-batch kernels (split-K
+  ``gemm``, ``act_backward_bias``).
+
+The large-batch routes that ``bench.py --model dl-mlp`` runs (x3 forward and
+data-gradient GEMMs, ``gemm_dact``, ``gemm_wgrad_bias``, the bf16 step at
+split-K 8) are pinned stage by stage in ``tests/test_dl_large_step_gpu.py``.
 
 Gradients, updated weights and both ADADELTA accumulators must match at
 rtol 1e-4 (fp32 MFMA accumulation vs float64)."""
 import numpy as np
 import pytest
 import torch
+
+from dlref import close as _close, reference as _reference
 
 pytestmark = pytest.mark.gpu
 
@@ -25,40 +36,6 @@ CASES = [
     ([21, 64, 1], 1, 100, True, 0.0),                       # one hidden layer (ADADELTA tail launch), regression
     ([16, 32, 32, 8], 1, 7, False, 0.0),                    # 8 classes, a batch smaller than one MFMA block
 ]
-
-
-def _reference(sizes, act, W0, X, y, regression, rho, eps, l2, Eg2_0, Edx2_0, layers):
-    """float64 autograd step: returns (grad, new flat, Eg2, Edx2)."""
-    flat = torch.from_numpy(W0).double().requires_grad_(True)
-    H = torch.from_numpy(X).double()
-    L = len(layers)
-    for i, (off, w, f) in enumerate(layers):
-        Wl = flat[off: off + w * f].view(w, f)
-        bl = flat[off + w * f: off + w * f + w]
-        Z = H @ Wl.T + bl
-        if i < L - 1:
-            H = torch.relu(Z) if act == 1 else torch.tanh(Z)
-        else:
-            H = Z
-    if regression:
-        loss = 0.5 * ((H[:, 0] - torch.from_numpy(y).double()) ** 2).mean()
-    else:
-        loss = torch.nn.functional.cross_entropy(H, torch.from_numpy(y).long())
-    loss.backward()
-    G = flat.grad.detach().clone()
-    Wn = flat.detach().clone()
-    g = G + l2 * Wn
-    Eg2 = rho * torch.from_numpy(Eg2_0).double() + (1 - rho) * g * g
-    Edx2 = torch.from_numpy(Edx2_0).double()
-    dx = -torch.sqrt(Edx2 + eps) / torch.sqrt(Eg2 + eps) * g
-    Edx2 = rho * Edx2 + (1 - rho) * dx * dx
-    return G.numpy(), (Wn + dx).numpy(), Eg2.numpy(), Edx2.numpy()
-
-
-def _close(name, got, want, rtol=1e-4):
-    scale = np.abs(want).max() + 1e-30
-    err = np.abs(got - want) / (np.abs(want) + 1e-3 * scale)
-    assert err.max() <= rtol, f"{name}: max rel err {err.max():.3g} at {int(err.argmax())}"
 
 
 @pytest.mark.parametrize("fused", [True, False])
@@ -96,6 +73,43 @@ def test_one_training_step_matches_autograd(case, fused, monkeypatch):
                                float(p["epsilon"]), l2, Eg2_0, Edx2_0, net.layers)
     _close("grad", net.grad.cpu().numpy(), G)
     _close("weights", net.flat.cpu().numpy(), Wn)
+    _close("Eg2", tr.Eg2.cpu().numpy(), E1)
+    _close("Edx2", tr.Edx2.cpu().numpy(), E2)
+
+
+def test_two_fused_steps_on_different_batch_tensors_match_autograd():
+    """The second call of FusedMlpStep._set_batch re-points F_0's A operand and the dW_0
+    job of Q_0 at a new batch tensor: a stale pointer in either would train on the first
+    batch again.  Two steps on two live tensors against two reference steps."""
+    from h2omx.models.deeplearning import H2ODeepLearningEstimator, _DLTrainer, _Net
+
+    sizes, act, M, l2 = [37, 48, 40, 3], 2, 50, 1e-4
+    dev = torch.device("cuda", 0)
+    rng = np.random.default_rng(7)
+    Xs = [rng.normal(size=(M, sizes[0])).astype(np.float32) for _ in range(2)]
+    ys = [rng.integers(0, sizes[-1], size=M).astype(np.int32) for _ in range(2)]
+    net = _Net(sizes, act, dev, torch.Generator().manual_seed(7))
+    p = dict(H2ODeepLearningEstimator.DEFAULTS)
+    p.update(l2=l2, loss="Automatic")
+    Xd = [torch.from_numpy(x).to(dev) for x in Xs]      # two live tensors: two different pointers
+    Yd = [torch.from_numpy(y).to(dev) for y in ys]
+    assert Xd[0].data_ptr() != Xd[1].data_ptr() and Yd[0].data_ptr() != Yd[1].data_ptr()
+    tr = _DLTrainer(p, net, Xd[0], Yd[0], act, True, False, 0.0, [0.0] * 8, M, 1, None,
+                    torch.Generator().manual_seed(1), None, len(sizes) - 2, backward=H2ODeepLearningEstimator._backward)
+    assert tr.fused is not None
+    P = net.flat.numel()
+    E1 = (rng.random(P) * 1e-4).astype(np.float32)
+    E2 = (rng.random(P) * 1e-6).astype(np.float32)
+    tr.Eg2.copy_(torch.from_numpy(E1))
+    tr.Edx2.copy_(torch.from_numpy(E2))
+    W = net.flat.cpu().numpy().copy()
+    for k in range(2):
+        tr._body(None, xb=Xd[k], yb=Yd[k])
+        G, W, E1, E2 = _reference(sizes, act, W, Xs[k], ys[k], False, float(p["rho"]), float(p["epsilon"]), l2,
+                                  E1, E2, net.layers)
+    torch.cuda.synchronize()
+    _close("grad", net.grad.cpu().numpy(), G)
+    _close("weights", net.flat.cpu().numpy(), W)
     _close("Eg2", tr.Eg2.cpu().numpy(), E1)
     _close("Edx2", tr.Edx2.cpu().numpy(), E2)
 
