@@ -736,8 +736,19 @@ class H2OApi:
             raise KeyError(fid)
         dest = params.get("predictions_frame") or f"prediction_{uuid.uuid4().hex[:10]}"
         kind = _predict_kind(params)
+        extra = {}
+        if kind == "contributions":
+            # H2O's baseline SHAP: background_frame (a frame key) and output_per_reference
+            if str(params.get("output_space", "false")).lower() == "true":
+                raise ValueError("output_space=true is not supported: contributions are in link space")
+            bg = unquote(str(params.get("background_frame") or "").strip('"'))
+            per_ref = str(params.get("output_per_reference", "false")).lower() == "true"
+            if bg and not isinstance(DKV.get(bg), Frame):
+                raise KeyError(bg)
+            if bg or per_ref:
+                extra = {"background_frame": bg or None, "output_per_reference": per_ref}
         self.cluster.run("predict", model=m.model_id, frame=fid, dest=dest, kind=kind,
-                         leaf_type=params.get("leaf_node_assignment_type") or "Path")
+                         leaf_type=params.get("leaf_node_assignment_type") or "Path", **extra)
         return m, dest
 
     def predict(self, mid, fid, params, **_):

@@ -157,8 +157,16 @@ class H2OConnection:
         j = self.wait_job(r["job"])
         return j["dest"]["name"]
 
-    def predict_contributions(self, model_id: str, frame: str) -> str:
-        r = self.request(f"POST /3/Predictions/models/{model_id}/frames/{frame}", {"predict_contributions": True})
+    def predict_contributions(self, model_id: str, frame: str, background_frame: str | None = None,
+                              output_per_reference: bool = False) -> str:
+        """SHAP contributions; with ``background_frame`` (a frame key) baseline SHAP against its rows,
+        averaged or (``output_per_reference``) one row per (row, background row)."""
+        data = {"predict_contributions": True}
+        if background_frame is not None:
+            data["background_frame"] = background_frame
+        if output_per_reference:
+            data["output_per_reference"] = True
+        r = self.request(f"POST /3/Predictions/models/{model_id}/frames/{frame}", data)
         return r["predictions_frame"]["name"]
 
     def partial_dependence(self, model_id: str, frame: str, cols=None, nbins: int = 20) -> list:

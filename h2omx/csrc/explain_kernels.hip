@@ -134,3 +134,199 @@ H2OMX_API int h2omx_tree_shap(const float* X, int64_t ld, int64_t n, int F, cons
 #undef LAUNCH_SHAP
   return launch_status();
 }
+
+// ---------------------------------------------------------------------------
+// Interventional (baseline) SHAP against a background set
+// ---------------------------------------------------------------------------
+// For a scored row x and a background row b the game value of a coalition T is
+// the margin of the hybrid row (features in T from x, the rest from b).  Per
+// flattened leaf with m unique-feature elements this is closed form: with
+// ox_j / ob_j = "x / b satisfies element j" (the follow rule above), the leaf
+// is dead when some element has neither; otherwise S = {ox && !ob}, a = |S|,
+// B = {!ox && ob}, c = |B| and
+//     phi_j += v (a-1)! c! / (a+c)!   for j in S,
+//     phi_j -= v a! (c-1)! / (a+c)!   for j in B.
+// Both weights come from one table T[a][c] = (a-1)! c! / (a+c)! (row 0 is
+// zero): wS = T[a][c], wB = T[c][a].
+//
+// shap_bg_mask_kernel packs ob for every (leaf, background row) into a
+// leaf-major word table [L][nb].  tree_shap_bg_kernel keeps one thread per
+// scored row: per leaf it packs ox once, then walks a chunk of background rows
+// whose ob words are wave-uniform scalar loads.  blockIdx.y is the background
+// chunk; each chunk owns a slab out[chunk][F][n] (no float atomics), and
+// shap_slab_mean_kernel adds the slabs in index order.
+namespace {
+
+constexpr int kBgW = 33;  // weight table is [33][33]: a, c <= 32
+
+__device__ __forceinline__ uint32_t elem_follows(float x, const float4 e, const uint32_t* __restrict__ sets) {
+  const int fi = __float_as_int(e.x);
+  if (x != x) return (uint32_t)((fi >> 30) & 1);
+  if ((fi >> 29) & 1) {
+    // categorical feature: the path's allowed level set (unseen levels: NA direction)
+    const int b = (int)x;
+    const uint32_t* st = sets + 8 * (int64_t)e.z;
+    return (b < 0 || b > 255) ? (uint32_t)((fi >> 30) & 1) : ((st[b >> 5] >> (b & 31)) & 1u);
+  }
+  return (x > e.z && x <= e.w) ? 1u : 0u;
+}
+
+// bit j of w spread over the word (0 or ~0).  Kept opaque: written as shifts the
+// compiler turns the mask-and-or below back into and / compare / select chains.
+__device__ __forceinline__ uint32_t bit_mask(uint32_t w, int j) {
+  uint32_t r;
+  asm("v_bfe_i32 %0, %1, %2, 1" : "=v"(r) : "v"(w), "i"(j));
+  return r;
+}
+
+__global__ __launch_bounds__(256) void shap_bg_mask_kernel(const float* __restrict__ B, int64_t ldb, int nb,
+                                                           const int4* __restrict__ leaves, int nleaves,
+                                                           const float4* __restrict__ elems,
+                                                           const uint32_t* __restrict__ sets,
+                                                           uint32_t* __restrict__ bmask) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= (int64_t)nleaves * nb) return;
+  const int L = (int)(i / nb);
+  const int b = (int)(i - (int64_t)L * nb);
+  const int4 hd = leaves[L];
+  const int m = hd.y < 32 ? hd.y : 32;
+  uint32_t mk = 0;
+  for (int j = 0; j < m; ++j) {
+    const float4 e = elems[hd.x + j];
+    const int f = __float_as_int(e.x) & 0x1FFFFFFF;
+    mk |= elem_follows(B[(int64_t)f * ldb + b], e, sets) << j;
+  }
+  bmask[i] = mk;
+}
+
+template <int MAXM, bool LDS>
+__global__ __launch_bounds__(256) void tree_shap_bg_kernel(const float* __restrict__ X, int64_t ld, int64_t n, int F,
+                                                           const int4* __restrict__ leaves, int nleaves,
+                                                           const float4* __restrict__ elems,
+                                                           const float* __restrict__ wtab,
+                                                           const uint32_t* __restrict__ sets,
+                                                           const uint32_t* __restrict__ bmask, int nb, int chunk,
+                                                           float* __restrict__ slabs) {
+  extern __shared__ float acc[];
+  __shared__ float w_s[kBgW * kBgW];
+  const int tid = threadIdx.x;
+  const int64_t r = (int64_t)blockIdx.x * 256 + tid;
+  const bool live = r < n;
+  const int64_t rr = live ? r : 0;
+  const int b0 = (int)blockIdx.y * chunk;
+  const int b1 = b0 + chunk < nb ? b0 + chunk : nb;
+  float* __restrict__ out = slabs + (int64_t)blockIdx.y * F * n;
+  for (int j = tid; j < kBgW * kBgW; j += 256) w_s[j] = wtab[j];
+  if (LDS)
+    for (int j = tid; j < F * 256; j += 256) acc[j] = 0.0f;
+  __syncthreads();
+  for (int L = 0; L < nleaves; ++L) {
+    const int4 hd = leaves[L];
+    const int m = hd.y;
+    if (m == 0) continue;
+    const float v = __int_as_float(hd.z);
+    int fe[MAXM];
+    float s[MAXM];
+    uint32_t ox = 0;
+#pragma unroll
+    for (int j = 0; j < MAXM; ++j) {
+      fe[j] = 0; s[j] = 0.0f;
+      if (j < m) {
+        const float4 e = elems[hd.x + j];
+        const int f = __float_as_int(e.x) & 0x1FFFFFFF;
+        ox |= elem_follows(X[(int64_t)f * ld + rr], e, sets) << j;
+        fe[j] = f;
+      }
+    }
+    const uint32_t mm = m >= 32 ? 0xFFFFFFFFu : ((1u << m) - 1u);
+    // leaf L's background words: L, b and nb are uniform, so these are scalar loads
+    const uint32_t* __restrict__ bm = bmask + (int64_t)L * nb;
+    for (int b = b0; b < b1; ++b) {
+      const uint32_t ob = bm[b];
+      const uint32_t S = ox & ~ob, Bs = ob & ~ox;
+      const bool dead = (~(ox | ob) & mm) != 0u;
+      const int a = __popc(S), c = __popc(Bs);
+      const uint32_t ws = __float_as_uint(w_s[dead ? 0 : a * kBgW + c]);
+      const uint32_t nwb = __float_as_uint(w_s[dead ? 0 : c * kBgW + a]) ^ 0x80000000u;
+#pragma unroll
+      for (int g = 0; g < MAXM; g += 4) {
+        if (g < m) {
+#pragma unroll
+          for (int j = g; j < g + 4; ++j) {
+            // S and Bs are disjoint: bit j sign-extended selects +wS, -wB or 0 without a branch
+            s[j] += __uint_as_float((bit_mask(S, j) & ws) | (bit_mask(Bs, j) & nwb));
+          }
+        }
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < MAXM; ++j) {
+      if (j < m) {
+        const float phi = v * s[j];
+        if (LDS) acc[fe[j] * 256 + tid] += phi;
+        else if (live) out[(int64_t)fe[j] * n + r] += phi;
+      }
+    }
+  }
+  if (LDS) {
+    __syncthreads();
+    if (live)
+      for (int f = 0; f < F; ++f) out[(int64_t)f * n + r] = acc[f * 256 + tid];
+  }
+}
+
+__global__ __launch_bounds__(256) void shap_slab_mean_kernel(const float* __restrict__ slabs, int nslabs, int64_t len,
+                                                             float div, float* __restrict__ out) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= len) return;
+  float s = 0.0f;
+  for (int c = 0; c < nslabs; ++c) s += slabs[(int64_t)c * len + i];
+  out[i] = s / div;
+}
+
+}  // namespace
+
+// Contributions of n scored rows against nb background rows.  bmask is
+// [nleaves][nb] scratch, slabs is [ceil(nb / chunk)][F][n] and must be zeroed
+// by the caller; chunk = 1 leaves phi(x, b) of pair (r, b) at slabs[b][f][r].
+// With out != null the slabs are added in index order and divided by nb into
+// out [F][n] (the averaged form).
+H2OMX_API int h2omx_tree_shap_background(const float* X, int64_t ld, int64_t n, int F, const float* B, int64_t ldb,
+                                         int nb, const void* leaves, int nleaves, const void* elems,
+                                         const float* wtab, int maxm, const uint32_t* sets, uint32_t* bmask,
+                                         int chunk, float* slabs, float* out, hipStream_t stream) {
+  if (n <= 0) return kOk;
+  if (F <= 0 || maxm < 1 || maxm > 32 || nb <= 0 || chunk <= 0 || nleaves < 0) return kBadArg;
+  const int64_t gx = (n + 255) / 256;
+  const int nchunks = (nb + chunk - 1) / chunk;
+  const int64_t cells = (int64_t)nleaves * nb;
+  if (gx > 0x7FFFFFFF || nchunks > 65535 || (cells + 255) / 256 > 0x7FFFFFFF) return kBadArg;
+  const int4* lv = reinterpret_cast<const int4*>(leaves);
+  const float4* el = reinterpret_cast<const float4*>(elems);
+  if (cells > 0)
+    hipLaunchKernelGGL(shap_bg_mask_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, stream, B, ldb, nb,
+                       lv, nleaves, el, sets, bmask);
+  const bool lds = (size_t)F * 256 * sizeof(float) <= 64 * 1024;
+  const size_t shm = lds ? (size_t)F * 256 * sizeof(float) : 0;
+  const dim3 grid((unsigned)gx, (unsigned)nchunks);
+#define LAUNCH_SHAP_BG(M)                                                                                        \
+  do {                                                                                                          \
+    if (lds)                                                                                                    \
+      hipLaunchKernelGGL((tree_shap_bg_kernel<M, true>), grid, dim3(256), shm, stream, X, ld, n, F, lv,         \
+                         nleaves, el, wtab, sets, bmask, nb, chunk, slabs);                                     \
+    else                                                                                                        \
+      hipLaunchKernelGGL((tree_shap_bg_kernel<M, false>), grid, dim3(256), 0, stream, X, ld, n, F, lv,          \
+                         nleaves, el, wtab, sets, bmask, nb, chunk, slabs);                                     \
+  } while (0)
+  if (maxm <= 8) LAUNCH_SHAP_BG(8);
+  else if (maxm <= 16) LAUNCH_SHAP_BG(16);
+  else LAUNCH_SHAP_BG(32);
+#undef LAUNCH_SHAP_BG
+  if (out != nullptr) {
+    const int64_t len = (int64_t)F * n;
+    if ((len + 255) / 256 > 0x7FFFFFFF) return kBadArg;
+    hipLaunchKernelGGL(shap_slab_mean_kernel, dim3((unsigned)((len + 255) / 256)), dim3(256), 0, stream, slabs,
+                       nchunks, len, (float)nb, out);
+  }
+  return launch_status();
+}

@@ -7,6 +7,9 @@ H2O).  Output columns are the predictors plus ``BiasTerm``; each row sums
 to the model's raw margin (link space).  On the GPU the contributions come
 from csrc/explain_kernels.hip (one thread per row over a flattened path
 table); on CPU frames the same path formula runs vectorised in NumPy.
+With ``background_frame=`` the same path table gives interventional
+(baseline) SHAP against every background row, averaged over the background
+or, with ``output_per_reference=True``, one row per (row, background row).
 
 ``partial_dependence(model, frame, col, nbins)`` (H2O PartialDependence):
 mean / sd / standard error of the model response with ``col`` forced to
@@ -20,7 +23,7 @@ import math
 import numpy as np
 import torch
 
-from .frame.frame import ENUM, Frame, Vec
+from .frame.frame import ENUM, INT, Frame, Vec
 from .models.base import ModelCategory
 
 
@@ -103,6 +106,30 @@ def _bucket(maxm: int) -> int:
     return 8 if maxm <= 8 else (16 if maxm <= 16 else 32)
 
 
+def _follows(X: np.ndarray, E: np.ndarray, sets=None):
+    """The follow rule of one leaf's elements E [m][4] on rows X [F][n]:
+    (features [m], o [m][n] float64 with o = 1 where the row satisfies the
+    element: lo < x <= hi, NA by na_ok, categorical levels by the path's level
+    set, out-of-range levels in the NA direction)."""
+    feats = E[:, 0].view(np.int32)
+    f = feats & 0x1FFFFFFF
+    na_ok = (feats >> 30) & 1
+    iscat = (feats >> 29) & 1
+    x = X[f]                                       # [m][n]
+    with np.errstate(invalid="ignore"):
+        o = np.where(np.isnan(x), na_ok[:, None].astype(np.float64),
+                     ((x > E[:, 2:3]) & (x <= E[:, 3:4])).astype(np.float64))
+    if sets is not None and iscat.any():
+        from .models.tree.structs import bitset_has
+
+        for j in np.nonzero(iscat)[0]:
+            c = np.where(np.isnan(x[j]), -1, x[j]).astype(np.int64)
+            oor = (c < 0) | (c > 255)
+            inside = bitset_has(sets[int(E[j, 2])], c).astype(np.float64)
+            o[j] = np.where(np.isnan(x[j]) | oor, float(na_ok[j]), inside)
+    return f, o
+
+
 def _shap_numpy(X: np.ndarray, lv, el, maxm, sets=None) -> np.ndarray:
     F, n = X.shape
     out = np.zeros((F, n), np.float64)
@@ -112,23 +139,8 @@ def _shap_numpy(X: np.ndarray, lv, el, maxm, sets=None) -> np.ndarray:
         if m == 0:
             continue
         E = el[start: start + m]
-        feats = E[:, 0].view(np.int32)
-        f = feats & 0x1FFFFFFF
-        na_ok = (feats >> 30) & 1
-        iscat = (feats >> 29) & 1
         z = E[:, 1].astype(np.float64)
-        x = X[f]                                       # [m][n]
-        with np.errstate(invalid="ignore"):
-            o = np.where(np.isnan(x), na_ok[:, None].astype(np.float64),
-                         ((x > E[:, 2:3]) & (x <= E[:, 3:4])).astype(np.float64))
-        if sets is not None and iscat.any():
-            from .models.tree.structs import bitset_has
-
-            for j in np.nonzero(iscat)[0]:
-                c = np.where(np.isnan(x[j]), -1, x[j]).astype(np.int64)
-                oor = (c < 0) | (c > 255)
-                inside = bitset_has(sets[int(E[j, 2])], c).astype(np.float64)
-                o[j] = np.where(np.isnan(x[j]) | oor, float(na_ok[j]), inside)
+        f, o = _follows(X, E, sets)
         P = np.zeros((m + 1, n))
         P[0] = 1.0
         for j in range(m):
@@ -151,12 +163,153 @@ def _shap_numpy(X: np.ndarray, lv, el, maxm, sets=None) -> np.ndarray:
     return out
 
 
-def predict_contributions(model, frame: Frame) -> Frame:
+def baseline_weights(M: int = 32) -> np.ndarray:
+    """T[a][c] = (a-1)! c! / (a+c)! for 1 <= a <= M, 0 <= c <= M (row 0 is
+    zero).  For a leaf whose elements split into a followed only by the scored
+    row and c followed only by the background row, T[a][c] is the Shapley
+    weight of the former and T[c][a] (negated) that of the latter."""
+    T = np.zeros((M + 1, M + 1), np.float64)
+    for a in range(1, M + 1):
+        for c in range(M + 1):
+            T[a, c] = math.factorial(a - 1) * math.factorial(c) / math.factorial(a + c)
+    return T
+
+
+def _shap_background_numpy(X: np.ndarray, B: np.ndarray, lv, el, maxm, sets=None,
+                           per_reference: bool = False) -> np.ndarray:
+    """Interventional SHAP of rows X [F][n] against background rows B [F][nb]
+    in float64: phi(x, b) per pair [F][n][nb] with ``per_reference``, else its
+    mean over the background [F][n]."""
+    F, n = X.shape
+    nb = B.shape[1]
+    T = baseline_weights(max(32, int(maxm)))
+    out = np.zeros((F, n, nb) if per_reference else (F, n), np.float64)
+    step = max(1, (1 << 22) // max(1, nb * max(1, int(maxm))))      # bounds the [m][rows][nb] temporaries
+    for start, m, vbits, _ in lv:
+        if m == 0:
+            continue
+        v = float(np.int32(vbits).view(np.float32))
+        E = el[start: start + m]
+        _, ob = _follows(B, E, sets)
+        ob = ob != 0
+        for r0 in range(0, n, step):
+            f, ox = _follows(X[:, r0: r0 + step], E, sets)
+            ox = ox != 0
+            only_x = ox[:, :, None] & ~ob[:, None, :]            # [m][rows][nb]
+            only_b = ~ox[:, :, None] & ob[:, None, :]
+            alive = (ox[:, :, None] | ob[:, None, :]).all(0)
+            a, c = only_x.sum(0), only_b.sum(0)
+            ws = np.where(alive, T[a, c], 0.0)
+            wb = np.where(alive, T[c, a], 0.0)
+            for j in range(m):
+                phi = v * (only_x[j] * ws - only_b[j] * wb)
+                if per_reference:
+                    out[f[j], r0: r0 + step] += phi
+                else:
+                    out[f[j], r0: r0 + step] += phi.sum(1)
+    return out if per_reference else out / nb
+
+
+_CPU_CONTRIB_LIMIT = 2 << 30
+
+
+def _background_chunk(n: int, nb: int, F: int, limit: int) -> int:
+    """Background rows per slab of the averaged form: enough chunks to give a
+    small scored frame ~1024 workgroups, as few slabs as that needs and as fit
+    in ``limit`` bytes."""
+    want = -(-1024 // max(1, -(-n // 256)))
+    fit = max(1, limit // max(1, F * n * 4))
+    return -(-nb // max(1, min(nb, want, fit)))
+
+
+def _shap_background_device(X: torch.Tensor, Bm: torch.Tensor, lv, el, maxm, sets, chunk: int,
+                            per_reference: bool) -> torch.Tensor:
+    """The HIP path: [F][n] mean over the background (slabs of ``chunk``
+    background rows, added in order), or [F][n * nb] x-major pairs."""
+    from .ops import P, check, explain_lib, stream
+
+    F, n = X.shape
+    nb = int(Bm.shape[1])
+    L = int(lv.shape[0])
+    chunk = 1 if per_reference else int(chunk)
+    nslabs = -(-nb // chunk)
+    dev = X.device
+    Xc = X.float().contiguous()
+    Bc = Bm.float().contiguous()
+    wt = torch.from_numpy(baseline_weights().astype(np.float32)).to(dev)
+    lvd = torch.from_numpy(np.ascontiguousarray(lv, np.int32) if L else np.zeros((1, 4), np.int32)).to(dev)
+    eld = torch.from_numpy(el if el.size else np.zeros((1, 4), np.float32)).to(dev)
+    setd = torch.from_numpy(sets.view(np.int32).copy()).to(dev)
+    bmask = torch.empty((max(L, 1), nb), dtype=torch.int32, device=dev)
+    slabs = torch.zeros((nslabs, F, n), dtype=torch.float32, device=dev)
+    out = None if per_reference else torch.empty((F, n), dtype=torch.float32, device=dev)
+    check(explain_lib().h2omx_tree_shap_background(
+        P(Xc), Xc.stride(0), n, F, P(Bc), Bc.stride(0), nb, P(lvd), L, P(eld), P(wt), maxm, P(setd), P(bmask),
+        chunk, P(slabs), P(out), stream(dev)), "tree_shap_background")
+    if per_reference:
+        return slabs.permute(1, 2, 0).reshape(F, n * nb)      # [b][f][r] -> x-major pairs
+    return out
+
+
+def _contributions_background(model, ens, X, Bm, lv, el, maxm, sets, per_reference: bool) -> Frame:
+    F, n = X.shape
+    nb = int(Bm.shape[1])
+    if nb == 0:
+        raise ValueError("background_frame has no rows")
+    Bm = Bm.to(X.device)
+    L = int(lv.shape[0])
+    result = 4 * n * (nb * (F + 3) if per_reference else F + 1)
+    if X.is_cuda:
+        if maxm > 32:
+            raise ValueError(f"a path of this model splits on {maxm} distinct features; the device kernel takes 32")
+        limit = torch.cuda.mem_get_info(X.device)[0] // 2
+        chunk = 1 if per_reference else _background_chunk(n, nb, F, limit)
+        nslabs = -(-nb // chunk)
+        slab = 4 * (nslabs * F * n + L * nb)
+    else:
+        limit, chunk, nslabs, slab = _CPU_CONTRIB_LIMIT, nb, 1, 0
+    if max(result, slab) > limit:
+        raise ValueError(f"predict_contributions of {n} rows against {nb} background rows needs {result} bytes for "
+                         f"the result and {slab} bytes of work space; the limit is {limit} bytes: use fewer "
+                         "background rows or score the frame in parts")
+    margin_b = ens.raw_margin(Bm)[0].float()
+    if X.is_cuda:
+        if nslabs > 65535:
+            raise ValueError(f"output_per_reference takes at most 65535 background rows on the device, got {nb}")
+        out = _shap_background_device(X, Bm, lv, el, maxm, sets, chunk, per_reference)
+    else:
+        ref = _shap_background_numpy(X.double().numpy(), Bm.double().numpy(), lv, el, maxm, sets, per_reference)
+        out = torch.from_numpy(ref.reshape(F, -1).astype(np.float32))
+    dev = out.device
+    vecs = []
+    if per_reference:
+        rows = torch.arange(n, dtype=torch.float32, device=dev)
+        refs = torch.arange(nb, dtype=torch.float32, device=dev)
+        vecs += [Vec("RowIdx", rows.repeat_interleave(nb), INT), Vec("BackgroundRowIdx", refs.repeat(n), INT)]
+        bias = margin_b.to(dev).repeat(n)
+    else:
+        bias = torch.full((n,), float(margin_b.double().mean()), dtype=torch.float32, device=dev)
+    vecs += [Vec(c, out[j], "real") for j, c in enumerate(model.x)]
+    vecs.append(Vec("BiasTerm", bias, "real"))
+    return Frame(vecs)
+
+
+def predict_contributions(model, frame: Frame, *, background_frame: Frame | None = None,
+                          output_per_reference: bool = False) -> Frame:
+    """Path-dependent TreeSHAP, or with ``background_frame`` interventional
+    (baseline) SHAP: every scored row x is explained against every background
+    row b by the Shapley values of the game "coalition features from x, the
+    rest from b".  The default averages over the background (one row per
+    scored row, ``BiasTerm`` = mean background margin);
+    ``output_per_reference`` returns one row per pair, x-major, led by
+    ``RowIdx`` and ``BackgroundRowIdx``, with ``BiasTerm`` = margin(b)."""
     ens = getattr(model, "ens", None)
     if ens is None or model.algo not in ("gbm", "drf", "xgboost", "generic"):
         raise NotImplementedError(f"predict_contributions is available for tree models, not {model.algo}")
     if ens.K != 1:
         raise NotImplementedError("predict_contributions supports regression and binomial tree models (as in H2O)")
+    if output_per_reference and background_frame is None:
+        raise ValueError("output_per_reference=True needs a background_frame")
     frame = model.adapt_frame(frame)
     X = model._matrix(frame) if hasattr(model, "_matrix") else frame.feature_matrix(model.x)
     F, n = X.shape
@@ -164,6 +317,10 @@ def predict_contributions(model, frame: Frame) -> Frame:
     scale = 1.0 / nt if (ens.average and nt > 0) else 1.0
     cb = getattr(ens, "catbits", None)
     lv, el, expected, maxm, sets = tree_paths(ens.trees[:nt], scale, None if cb is None else cb[:nt])
+    if background_frame is not None:
+        bg = model.adapt_frame(background_frame)
+        Bm = model._matrix(bg) if hasattr(model, "_matrix") else bg.feature_matrix(model.x)
+        return _contributions_background(model, ens, X, Bm, lv, el, maxm, sets, bool(output_per_reference))
     bias = expected + (0.0 if ens.average else float(ens.init_f[0]))
     if X.is_cuda:
         from .ops import P, check, explain_lib, stream

@@ -136,9 +136,7 @@ def feature_frequencies(model, frame: Frame) -> Frame:
     return Frame([Vec(c, cnt[j], "real") for j, c in enumerate(model.x)])
 
 
-def glm_contributions(model, frame: Frame) -> Frame:
-    if model.algo not in ("glm", "gam") or model.family == "multinomial" or model.family == "ordinal":
-        raise NotImplementedError("linear contributions: single-output GLMs")
+def _glm_design(model, frame: Frame) -> torch.Tensor:
     frame = model.adapt_frame(frame)
     spec = getattr(model, "interaction_spec", None)
     if spec:
@@ -146,7 +144,53 @@ def glm_contributions(model, frame: Frame) -> Frame:
 
         frame = apply_interactions(frame, spec)
     d = model.design
-    Xs = d.transform(d.raw_matrix(frame)).double()
+    return d.transform(d.raw_matrix(frame)).double()
+
+
+def _glm_contributions_background(model, Xs: torch.Tensor, Bs: torch.Tensor, per_reference: bool) -> Frame:
+    """Linear model against a background: phi_j(x, b) = beta_j (x_j - b_j) per
+    design column, grouped by predictor; BiasTerm = eta(b)."""
+    d = model.design
+    p, n = Xs.shape
+    nb = Bs.shape[1]
+    if nb == 0:
+        raise ValueError("background_frame has no rows")
+    Bs = Bs.to(Xs.device)
+    b = torch.from_numpy(model.beta_std[0].astype(np.float64)).to(Xs.device)
+    eta_b = (b[:p, None] * Bs).sum(0) + b[p]
+    if per_reference:
+        if 8 * p * n * nb > (2 << 30):
+            raise ValueError(f"output_per_reference of {n} rows against {nb} background rows is too large; use "
+                             "fewer background rows or score the frame in parts")
+        contrib = (b[:p, None, None] * (Xs[:, :, None] - Bs[:, None, :])).reshape(p, n * nb)
+        bias = eta_b.repeat(n)
+    else:
+        contrib = b[:p, None] * (Xs - Bs.mean(1, keepdim=True))
+        bias = eta_b.mean().expand(n)
+    vecs = []
+    if per_reference:
+        dev = Xs.device
+        vecs += [Vec("RowIdx", torch.arange(n, dtype=torch.float32, device=dev).repeat_interleave(nb), "int"),
+                 Vec("BackgroundRowIdx", torch.arange(nb, dtype=torch.float32, device=dev).repeat(n), "int")]
+    for c in d.x:
+        js = [j for j, (col, _) in enumerate(d.spec) if col == c]
+        if js:
+            vecs.append(Vec(c, contrib[js].sum(0).float(), "real"))
+    vecs.append(Vec("BiasTerm", bias.float().contiguous(), "real"))
+    return Frame(vecs)
+
+
+def glm_contributions(model, frame: Frame, *, background_frame: Frame | None = None,
+                      output_per_reference: bool = False) -> Frame:
+    if model.algo not in ("glm", "gam") or model.family == "multinomial" or model.family == "ordinal":
+        raise NotImplementedError("linear contributions: single-output GLMs")
+    if output_per_reference and background_frame is None:
+        raise ValueError("output_per_reference=True needs a background_frame")
+    d = model.design
+    Xs = _glm_design(model, frame)
+    if background_frame is not None:
+        return _glm_contributions_background(model, Xs, _glm_design(model, background_frame),
+                                             bool(output_per_reference))
     b = torch.from_numpy(model.beta_std[0].astype(np.float64)).to(Xs.device)
     p = Xs.shape[0]
     # standardised design columns are centred at the training means: x_std = (x - mean) / sd

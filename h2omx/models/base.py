@@ -155,11 +155,14 @@ class Model:
     def varimp(self) -> list[tuple]:
         return []
 
-    def predict_contributions(self, frame: Frame) -> Frame:
-        """SHAP contributions + BiasTerm (tree models; h2omx.explain)."""
+    def predict_contributions(self, frame: Frame, *, background_frame: Frame | None = None,
+                              output_per_reference: bool = False) -> Frame:
+        """SHAP contributions + BiasTerm (tree models; h2omx.explain).  With ``background_frame``:
+        interventional SHAP against its rows, averaged or (``output_per_reference``) pair by pair."""
         from ..explain import predict_contributions
 
-        return predict_contributions(self, frame)
+        return predict_contributions(self, frame, background_frame=background_frame,
+                                     output_per_reference=output_per_reference)
 
     # -- h2omx.explain_more (H2O model introspection APIs) ---------------------
     def predict_leaf_node_assignment(self, frame: Frame, type: str = "Path") -> Frame:  # noqa: A002

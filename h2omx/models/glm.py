@@ -217,11 +217,13 @@ class GLMModel(Model):
             return torch.stack([1 - mu, mu]).float()
         return mu[None, :].float()
 
-    def predict_contributions(self, frame: Frame) -> Frame:
+    def predict_contributions(self, frame: Frame, *, background_frame: Frame | None = None,
+                              output_per_reference: bool = False) -> Frame:
         """Exact linear SHAP values in link space (explain_more.glm_contributions)."""
         from ..explain_more import glm_contributions
 
-        return glm_contributions(self, frame)
+        return glm_contributions(self, frame, background_frame=background_frame,
+                                 output_per_reference=output_per_reference)
 
     def varimp(self):
         b = np.abs(self.beta_std[:, :-1]).sum(0)

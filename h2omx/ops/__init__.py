@@ -126,6 +126,8 @@ METRICS_SIGS = {
 
 EXPLAIN_SIGS = {
     "h2omx_tree_shap": "PLLIPIPPIPPS",
+    # X, ld, n, F, B, ldb, nb, leaves, nleaves, elems, wtab, maxm, sets, bmask, chunk, slabs, out
+    "h2omx_tree_shap_background": "PLLIPLIPIPPIPPIPPS",
 }
 
 P2P_SIGS = {

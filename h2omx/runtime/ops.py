@@ -180,10 +180,23 @@ def op_train(cl, algo, params, x=None, y=None, training_frame=None, validation_f
     return m.model_id
 
 
-def op_predict(cl, model, frame, dest, kind="predict", leaf_type="Path"):
+def op_predict(cl, model, frame, dest, kind="predict", leaf_type="Path", background_frame=None,
+               output_per_reference=False):
     m = _model(model)
     fr = _frame(frame)
-    if kind == "contributions":
+    if kind != "contributions" and (background_frame or output_per_reference):
+        raise ValueError("background_frame and output_per_reference belong to predict_contributions")
+    if kind == "contributions" and (background_frame or output_per_reference):
+        if not background_frame:
+            raise ValueError("output_per_reference=True needs a background_frame")
+        # every rank explains its shard of the scored rows against all background rows
+        comm = cl.comm if cl.world_size > 1 else None
+        bg = gather_frame(_frame(background_frame), comm)
+        pf = m.predict_contributions(fr, background_frame=bg, output_per_reference=bool(output_per_reference))
+        if output_per_reference and comm is not None:
+            counts = comm.all_gather_cat(torch.tensor([fr.nrows], dtype=torch.int64, device=fr.device))
+            pf.vec("RowIdx").data += float(counts[:cl.rank].sum())     # RowIdx counts rows of the whole frame
+    elif kind == "contributions":
         pf = m.predict_contributions(fr)
     elif kind == "leaf_nodes":
         pf = m.predict_leaf_node_assignment(fr, leaf_type)
