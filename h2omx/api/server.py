@@ -17,6 +17,7 @@ build models, score and download MOJOs:
   POST /3/ModelMetrics/models/{m}/frames/{f}
   POST /3/Predictions/...?predict_contributions=true  (TreeSHAP)
   POST /3/PartialDependence  GET /3/PartialDependence/{id}
+  POST /3/FriedmansPopescusH  (H statistic: model_id, frame, variables)
   POST /99/Grid/{algo}       GET /99/Grids[/{id}]
   POST /99/AutoMLBuilder     GET /99/AutoML/{id}    GET /99/Leaderboards/{id}
   POST /99/Rapids            DELETE /3/DKV[/{key}]  POST /3/Shutdown
@@ -227,6 +228,7 @@ class H2OApi:
         R("GET", r"/99/Leaderboards/(?P<aid>[^/]+)", self.leaderboard)
         R("POST", r"/3/PartialDependence/?", self.partial_dependence)
         R("GET", r"/3/PartialDependence/(?P<pid>[^/]+)", self.partial_dependence_get)
+        R("POST", r"/3/FriedmansPopescusH/?", self.friedman_h)
         R("POST", r"/99/Rapids", self.rapids)
         R("DELETE", r"/3/DKV", self.delete_all)
         R("DELETE", r"/3/DKV/(?P<key>[^/]+)", self.delete_key)
@@ -818,6 +820,18 @@ class H2OApi:
                                           [[d[c] for c in names] for d in r["data"]]))
         return {"__meta": S.meta("PartialDependenceV3", "PartialDependence"),
                 "destination_key": S.key_ref(pid, "Key<PartialDependence>"), "partial_dependence_data": tables}
+
+    # -- Friedman-Popescu H statistic ---------------------------------------------
+    def friedman_h(self, params, **_):
+        m = self._get_model(str(params.get("model_id") or "").strip('"'))
+        fid = unquote(str(params.get("frame") or "").strip('"'))
+        if not isinstance(DKV.get(fid), Frame):
+            raise KeyError(fid)
+        variables = [str(v) for v in parse_list(params.get("variables"))]
+        h = self.cluster.run("friedman_h", model=m.model_id, frame=fid, variables=variables)
+        return {"__meta": S.meta("FriedmanPopescusHV3", "FriedmanPopescusH"),
+                "model_id": S.key_ref(m.model_id, "Key<Model>"), "frame": S.key_ref(fid, "Key<Frame>"),
+                "variables": variables, "h": _jsonable(h)}
 
     # -- AutoML ---------------------------------------------------------------
     def automl_build(self, params, body, **_):

@@ -177,6 +177,12 @@ class H2OConnection:
         self.wait_job(r["job"])
         return self.request(f"GET /3/PartialDependence/{r['destination_key']['name']}")["partial_dependence_data"]
 
+    def h(self, model_id: str, frame: str, variables) -> float:
+        """Friedman and Popescu's H statistic of ``variables`` (H2O ``model.h``); NaN where it is undefined."""
+        r = self.request("POST /3/FriedmansPopescusH", {"model_id": model_id, "frame": frame,
+                                                        "variables": list(variables)})
+        return float(r["h"])
+
     def model_performance(self, model_id: str, frame: str) -> dict:
         return self.request(f"POST /3/ModelMetrics/models/{model_id}/frames/{frame}")["model_metrics"][0]
 

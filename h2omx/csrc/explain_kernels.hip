@@ -330,3 +330,136 @@ H2OMX_API int h2omx_tree_shap_background(const float* X, int64_t ld, int64_t n, 
   }
   return launch_status();
 }
+
+// ---------------------------------------------------------------------------
+// Friedman-Popescu H statistic: partial dependence of every variable subset
+// ---------------------------------------------------------------------------
+// The partial dependence of the model on a variable set S by the weighted tree
+// traversal is a sum over the flattened leaves:
+//     PD_S(x) = sum_l v_l prod_{e in l, feat(e) in S} [x follows e] prod_{e in l, feat(e) not in S} z_e.
+// For k variables the host keeps the leaves whose path touches one of them and
+// gives each a record: hdr [2k + 2] = {lo_0, hi_0, ..., lo_{k-1}, hi_{k-1},
+// na_ok mask, untouched mask} and w [2^k] doubles, w[S] = v prod_{e not in S}
+// z_e for the subset with bit mask S (w[0] pads; 0 where S holds no touched
+// variable: that term is the same for every row and stays on the host).  One
+// thread per row builds the k-bit follow mask of its row per leaf and adds
+// w[S] for every S the mask covers, in fp64 registers: H is a difference of
+// partial dependences that cancels to zero for variables that do not interact.
+// The leaf record is wave-uniform (scalar loads).  blockIdx.y is a chunk of
+// leaves; each chunk owns a slab Fd[chunk][2^k - 1][n] (no fp64 atomics), and
+// h_slab_sum_kernel adds the slabs in index order.
+namespace {
+
+constexpr int kHMaxK = 6;
+constexpr int kHGroup = 16;
+
+struct HVars {
+  int f[kHMaxK];
+};
+
+template <int K>
+__global__ __launch_bounds__(256) void friedman_h_pd_kernel(const float* __restrict__ X, int64_t ld, int64_t n,
+                                                            HVars vars, const float* __restrict__ hdr,
+                                                            const double* __restrict__ w, int nleaves, int chunk,
+                                                            double* __restrict__ Fd) {
+  constexpr int NS = (1 << K) - 1, HW = 2 * K + 2;
+  const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const bool live = r < n;
+  const int64_t rr = live ? r : 0;
+  float x[K];
+  uint32_t isna = 0;
+#pragma unroll
+  for (int j = 0; j < K; ++j) {
+    x[j] = X[(int64_t)vars.f[j] * ld + rr];
+    isna |= (x[j] != x[j] ? 1u : 0u) << j;
+  }
+  const int l0 = (int)blockIdx.y * chunk;
+  const int l1 = l0 + chunk < nleaves ? l0 + chunk : nleaves;
+  double acc[NS];
+#pragma unroll
+  for (int s = 0; s < NS; ++s) acc[s] = 0.0;
+  for (int L = l0; L < l1; ++L) {
+    // L is uniform: the record arrives as scalar loads.  Every load is unconditional (a load under
+    // the row's condition would become a branch around a scalar load and its wait).
+    const float* __restrict__ h = hdr + (int64_t)L * HW;
+    const double* __restrict__ wl = w + ((int64_t)L << K);
+    float hv[HW];
+#pragma unroll
+    for (int j = 0; j < HW; ++j) hv[j] = h[j];
+    uint32_t in = 0;
+#pragma unroll
+    for (int j = 0; j < K; ++j) in |= ((uint32_t)(x[j] > hv[2 * j]) & (uint32_t)(x[j] <= hv[2 * j + 1])) << j;
+    // a NaN compares false above and follows the path's NA direction
+    const uint32_t mk = in | (isna & __float_as_uint(hv[2 * K])) | __float_as_uint(hv[2 * K + 1]);
+    // weights in groups of 16 doubles (32 SGPRs); w[0] is padding.  The fence keeps the scheduler
+    // from hoisting every group's loads to the top of the body, which runs out of SGPRs at K >= 5.
+#pragma unroll
+    for (int g = 0; g <= NS; g += kHGroup) {
+      double wv[kHGroup];
+#pragma unroll
+      for (int i = 0; i < kHGroup; ++i) wv[i] = (g + i <= NS) ? wl[g + i] : 0.0;
+#pragma unroll
+      for (int i = 0; i < kHGroup; ++i) {
+        const int S = g + i;
+        // acc += w * (1.0 or 0.0): one select on the multiplier's high word, the weight stays scalar
+        if (S >= 1 && S <= NS)
+          acc[S - 1] = fma(wv[i], __hiloint2double(((mk & S) == S) ? 0x3FF00000 : 0, 0), acc[S - 1]);
+      }
+      if (NS >= kHGroup) __builtin_amdgcn_sched_barrier(0);
+    }
+  }
+  if (live) {
+    double* __restrict__ out = Fd + (int64_t)blockIdx.y * NS * n + r;
+#pragma unroll
+    for (int s = 0; s < NS; ++s) out[(int64_t)s * n] = acc[s];
+  }
+}
+
+__global__ __launch_bounds__(256) void h_slab_sum_kernel(const double* __restrict__ slabs, int nslabs, int64_t len,
+                                                         double* __restrict__ out) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= len) return;
+  double s = 0.0;
+  for (int c = 0; c < nslabs; ++c) s += slabs[(int64_t)c * len + i];
+  out[i] = s;
+}
+
+}  // namespace
+
+// Partial dependence of n rows on every non-empty subset of k variables (2 <= k
+// <= 6, feature rows v0 .. v5 of X, the first k used).  hdr is [nleaves][2k + 2],
+// w is [nleaves][2^k]; leaves are cut into chunks of `chunk`.  One chunk
+// writes out [2^k - 1][n] directly; more write slabs [nchunks][2^k - 1][n], which
+// are then added in index order into out.
+H2OMX_API int h2omx_friedman_h_pd(const float* X, int64_t ld, int64_t n, int F, int k, int v0, int v1, int v2, int v3,
+                                  int v4, int v5, const float* hdr, const double* w, int nleaves, int chunk,
+                                  double* slabs, double* out, hipStream_t stream) {
+  if (n <= 0 || nleaves <= 0) return kOk;
+  if (k < 2 || k > kHMaxK || chunk <= 0 || ld < n) return kBadArg;
+  const HVars vars = {{v0, v1, v2, v3, v4, v5}};
+  for (int j = 0; j < k; ++j)
+    if (vars.f[j] < 0 || vars.f[j] >= F) return kBadArg;
+  const int64_t gx = (n + 255) / 256;
+  const int nchunks = (nleaves + chunk - 1) / chunk;
+  const int64_t len = (((int64_t)1 << k) - 1) * n;
+  if (gx > 0x7FFFFFFF || nchunks > 65535 || (len + 255) / 256 > 0x7FFFFFFF) return kBadArg;
+  double* Fd = nchunks == 1 ? out : slabs;
+  const dim3 grid((unsigned)gx, (unsigned)nchunks);
+#define LAUNCH_H(KK)                                                                                             \
+  case KK:                                                                                                      \
+    hipLaunchKernelGGL((friedman_h_pd_kernel<KK>), grid, dim3(256), 0, stream, X, ld, n, vars, hdr, w, nleaves, \
+                       chunk, Fd);                                                                              \
+    break
+  switch (k) {
+    LAUNCH_H(2);
+    LAUNCH_H(3);
+    LAUNCH_H(4);
+    LAUNCH_H(5);
+    LAUNCH_H(6);
+  }
+#undef LAUNCH_H
+  if (nchunks > 1)
+    hipLaunchKernelGGL(h_slab_sum_kernel, dim3((unsigned)((len + 255) / 256)), dim3(256), 0, stream, slabs, nchunks,
+                       len, out);
+  return launch_status();
+}

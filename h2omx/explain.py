@@ -11,6 +11,11 @@ With ``background_frame=`` the same path table gives interventional
 (baseline) SHAP against every background row, averaged over the background
 or, with ``output_per_reference=True``, one row per (row, background row).
 
+``friedman_h(model, frame, variables)`` (H2O ``model.h``): Friedman and
+Popescu's H statistic of 2 or more numerical variables, from the partial
+dependence of every subset of them by the weighted tree traversal, summed
+over the same path table in float64 (friedman_h_pd_kernel on the GPU).
+
 ``partial_dependence(model, frame, col, nbins)`` (H2O PartialDependence):
 mean / sd / standard error of the model response with ``col`` forced to
 each grid value (``nbins`` equally spaced values between the column's min
@@ -340,6 +345,208 @@ def predict_contributions(model, frame: Frame, *, background_frame: Frame | None
     vecs = [Vec(c, out[j], "real") for j, c in enumerate(model.x)]
     vecs.append(Vec("BiasTerm", torch.full((n,), float(bias), dtype=torch.float32, device=out.device), "real"))
     return Frame(vecs)
+
+
+# ---------------------------------------------------------------------------
+# Friedman-Popescu H statistic
+# ---------------------------------------------------------------------------
+H_MAX_VARS = 10          # NumPy path
+H_MAX_VARS_DEVICE = 6    # friedman_h_pd_kernel<K> is instantiated for K = 2 .. 6
+
+
+def _h_leaf_table(lv, el, var_idx) -> dict:
+    """Host records of the H statistic's partial dependence on the variables
+    ``var_idx`` (feature rows, bit j of a subset mask S stands for
+    ``var_idx[j]``), from the path table of :func:`tree_paths`.  Leaves whose
+    path touches a variable are kept: ``hdr`` [L][2k + 2] float32 = {lo_j, hi_j
+    per variable (-inf, +inf where untouched), na_ok mask, untouched mask (both
+    as bits)} and ``w`` [L][2^k] float64 with w[S] = v prod_{e not in S} z_e
+    (float64 products of the table's float32 z; w[0] pads).  A term that no
+    row can switch off, S without a touched variable or a leaf that touches
+    none, is the same for every row: it is left out of ``w`` (zero) and summed
+    into ``const`` [2^k - 1]."""
+    k = len(var_idx)
+    nsub1 = 1 << k
+    S = np.arange(nsub1)
+    inS = ((S[:, None] >> np.arange(k)) & 1).astype(bool)                # [2^k][k]
+    pos = {int(f): j for j, f in enumerate(var_idx)}
+    hdr, w = [], []
+    const = np.zeros(nsub1, np.float64)
+    for start, m, vbits, _ in lv:
+        v = float(np.int32(vbits).view(np.float32))
+        E = el[start: start + m]
+        feats = E[:, 0].view(np.int32)
+        h = np.empty(2 * k + 2, np.float32)
+        h[0:2 * k:2], h[1:2 * k:2] = -np.inf, np.inf
+        z = np.ones(k, np.float64)
+        touched = na = 0
+        other = 1.0
+        for e, fi in zip(E, feats):
+            j = pos.get(int(fi) & 0x1FFFFFFF)
+            if j is None:
+                other *= float(e[1])
+                continue
+            h[2 * j], h[2 * j + 1] = e[2], e[3]
+            z[j] = float(e[1])
+            touched |= 1 << j
+            na |= ((int(fi) >> 30) & 1) << j
+        ws = v * other * np.where(inS, 1.0, z).prod(1)
+        fold = (S & touched) == 0
+        const += np.where(fold, ws, 0.0)
+        if touched:
+            untouched = (nsub1 - 1) & ~touched
+            h[2 * k:] = np.array([na | untouched, untouched], np.uint32).view(np.float32)
+            hdr.append(h)
+            w.append(np.where(fold, 0.0, ws))
+    return {"k": k, "vars": [int(f) for f in var_idx], "const": const[1:].copy(),
+            "hdr": np.asarray(hdr, np.float32).reshape(-1, 2 * k + 2),
+            "w": np.asarray(w, np.float64).reshape(-1, nsub1)}
+
+
+def _h_pd_numpy(X: np.ndarray, table: dict, const: bool = True) -> np.ndarray:
+    """Partial dependence [2^k - 1][n] of rows X [F][n] on every non-empty
+    subset of the table's variables, in float64 (row S - 1 is subset S; the
+    model's link space without ``init_f``).  ``const=False`` leaves the
+    row-independent part out."""
+    k, hdr, w = table["k"], table["hdr"], table["w"]
+    nsub = (1 << k) - 1
+    n = X.shape[1]
+    L = hdr.shape[0]
+    out = np.zeros((nsub, n), np.float64)
+    x = X[table["vars"]]                                                 # [k][n]
+    words = hdr[:, 2 * k:].view(np.uint32).astype(np.int64)              # [L][2] = na_ok, untouched
+    step = max(1, (1 << 22) // max(1, L))                                # bounds the [L][rows] temporaries
+    for r0 in range(0, n if L else 0, step):
+        xs = x[:, r0: r0 + step]
+        mk = np.repeat(words[:, 1:2], xs.shape[1], 1)
+        for j in range(k):
+            with np.errstate(invalid="ignore"):
+                o = np.where(np.isnan(xs[j])[None, :], ((words[:, 0:1] >> j) & 1) != 0,
+                             (xs[j][None, :] > hdr[:, 2 * j, None]) & (xs[j][None, :] <= hdr[:, 2 * j + 1, None]))
+            mk |= o.astype(np.int64) << j
+        for s in range(1, nsub + 1):
+            out[s - 1, r0: r0 + step] = (((mk & s) == s) * w[:, s, None]).sum(0)
+    if const:
+        out += table["const"][:, None]
+    return out
+
+
+def _h_chunks(n: int, L: int, nsub: int, limit: int) -> int:
+    """Leaf chunks of the device path: enough to give a small frame ~1024
+    workgroups (as ``_background_chunk``), as many as fit in ``limit`` bytes
+    next to the result; the sized ValueError when one does not fit."""
+    one = 8 * nsub * n
+    if one > limit:
+        raise ValueError(f"the H statistic of {nsub} variable subsets on {n} rows needs {one} bytes of work space; "
+                         f"the limit is {limit} bytes: use a sample of the rows")
+    want = -(-1024 // max(1, -(-n // 256)))
+    fit = max(1, limit // max(1, one) - 1)
+    return max(1, min(L, want, fit, 65535))
+
+
+def _h_pd_device(X: torch.Tensor, table: dict, nchunks: int | None = None, const: bool = True) -> torch.Tensor:
+    """The HIP path of :func:`_h_pd_numpy`: [2^k - 1][n] float64 on X's device.
+    Leaves go to ``nchunks`` slabs that are added in order."""
+    from .ops import P, check, explain_lib, stream
+
+    k, hdr, w = table["k"], table["hdr"], table["w"]
+    if not 2 <= k <= H_MAX_VARS_DEVICE:
+        raise ValueError(f"the device kernel takes 2 to {H_MAX_VARS_DEVICE} variables, got {k}")
+    nsub = (1 << k) - 1
+    F, n = X.shape
+    L = int(hdr.shape[0])
+    dev = X.device
+    if nchunks is None:
+        nchunks = _h_chunks(n, L, nsub, torch.cuda.mem_get_info(dev)[0] // 2)
+    out = torch.zeros((nsub, n), dtype=torch.float64, device=dev)
+    if L and n:
+        chunk = -(-L // max(1, min(int(nchunks), L)))
+        nchunks = -(-L // chunk)
+        Xc = X.float().contiguous()
+        hd = torch.from_numpy(np.ascontiguousarray(hdr)).to(dev)
+        wd = torch.from_numpy(np.ascontiguousarray(w)).to(dev)
+        slabs = torch.empty((nchunks, nsub, n), dtype=torch.float64, device=dev) if nchunks > 1 else None
+        v = table["vars"] + [0] * (H_MAX_VARS_DEVICE - k)
+        check(explain_lib().h2omx_friedman_h_pd(P(Xc), max(int(Xc.stride(0)), n), n, F, k, *v, P(hd), P(wd), L, chunk,
+                                                P(slabs), P(out), stream(dev)), "friedman_h_pd")
+    if const:
+        out += torch.from_numpy(table["const"]).to(dev)[:, None]
+    return out
+
+
+def _h_sums(Fd: torch.Tensor) -> torch.Tensor:
+    """[nsub + 1] float64: the sum of every subset's partial dependence over
+    the rows, then the row count (additive over row shards)."""
+    cnt = torch.tensor([float(Fd.shape[1])], dtype=torch.float64, device=Fd.device)
+    return torch.cat([Fd.double().sum(1), cnt])
+
+
+def _h_moments(Fd: torch.Tensor, means: torch.Tensor) -> torch.Tensor:
+    """[2] float64 = {num, den} of H^2 over the rows of Fd [2^k - 1][n], the
+    partial dependences centred by ``means`` [2^k - 1] (additive over row
+    shards): num = sum_i (sum_S (-1)^(k - |S|) F~_S(x_i))^2, den = sum_i
+    F~_full(x_i)^2."""
+    nsub = Fd.shape[0]
+    k = nsub.bit_length()
+    sign = torch.tensor([(-1.0) ** (k - bin(s).count("1")) for s in range(1, nsub + 1)], dtype=torch.float64,
+                        device=Fd.device)
+    C = Fd.double() - means.to(Fd.device)[:, None]
+    comb = (sign[:, None] * C).sum(0)
+    return torch.stack([(comb * comb).sum(), (C[-1] * C[-1]).sum()])
+
+
+def friedman_h(model, frame: Frame, variables, *, comm=None) -> float:
+    """Friedman and Popescu's H statistic of ``variables`` (H2O ``model.h``):
+    the share of the variance of their joint partial dependence that no
+    proper subset explains, 0 for variables that do not interact.  The
+    partial dependence is the weighted tree traversal evaluated on every row
+    of ``frame``; NaN when the joint partial dependence does not vary or the
+    ratio is not below one."""
+    ens = getattr(model, "ens", None)
+    if ens is None or model.algo not in ("gbm", "drf", "xgboost", "generic"):
+        raise NotImplementedError(f"the H statistic is available for tree models, not {model.algo}")
+    if ens.K != 1:
+        raise NotImplementedError("the H statistic supports regression and binomial tree models (as in H2O)")
+    variables = [variables] if isinstance(variables, str) else list(variables)
+    if len(variables) < 2:
+        raise ValueError(f"the H statistic needs at least 2 variables, got {variables}")
+    for i, v in enumerate(variables):
+        if v in variables[:i]:
+            raise ValueError(f"variable {v!r} is listed twice")
+        if v not in model.x:
+            raise ValueError(f"variable {v!r} is not a predictor of the model")
+        if model.feature_types.get(v) == ENUM:
+            raise ValueError(f"variable {v!r} is categorical: the H statistic takes numerical variables only")
+    frame = model.adapt_frame(frame)
+    X = model._matrix(frame) if hasattr(model, "_matrix") else frame.feature_matrix(model.x)
+    k = len(variables)
+    kmax = H_MAX_VARS_DEVICE if X.is_cuda else H_MAX_VARS
+    if k > kmax:
+        raise ValueError(f"the H statistic takes at most {kmax} variables on "
+                         f"{'the device' if X.is_cuda else 'the CPU'}, got {k}: {variables[kmax]!r} is one too many")
+    n = int(X.shape[1])
+    nsub = (1 << k) - 1
+    nt = ens.ntrees
+    scale = 1.0 / nt if (ens.average and nt > 0) else 1.0
+    cb = getattr(ens, "catbits", None)
+    lv, el, _, _, _ = tree_paths(ens.trees[:nt], scale, None if cb is None else cb[:nt])
+    table = _h_leaf_table(lv, el, [model.x.index(v) for v in variables])
+    # the row-independent part cancels in the centring and stays out: a variable that no tree uses
+    # then has an exactly zero partial dependence
+    if X.is_cuda:
+        nchunks = _h_chunks(n, int(table["hdr"].shape[0]), nsub, torch.cuda.mem_get_info(X.device)[0] // 2)
+        Fd = _h_pd_device(X, table, nchunks, const=False)
+    else:
+        _h_chunks(n, 1, nsub, _CPU_CONTRIB_LIMIT)
+        Fd = torch.from_numpy(_h_pd_numpy(X.double().numpy(), table, const=False))
+    sums = _h_sums(Fd)
+    if comm is not None and comm.world_size > 1:
+        comm.all_reduce_(sums)
+    mom = _h_moments(Fd, sums[:-1] / sums[-1].clamp(min=1.0))
+    if comm is not None and comm.world_size > 1:
+        comm.all_reduce_(mom)
+    num, den = (float(a) for a in mom)
+    return math.sqrt(num / den) if num < den else float("nan")
 
 
 # ---------------------------------------------------------------------------

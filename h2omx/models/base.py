@@ -164,6 +164,12 @@ class Model:
         return predict_contributions(self, frame, background_frame=background_frame,
                                      output_per_reference=output_per_reference)
 
+    def h(self, frame: Frame, variables) -> float:
+        """Friedman and Popescu's H statistic of 2 or more numerical predictors (tree models; h2omx.explain)."""
+        from ..explain import friedman_h
+
+        return friedman_h(self, frame, variables, comm=self.comm)
+
     # -- h2omx.explain_more (H2O model introspection APIs) ---------------------
     def predict_leaf_node_assignment(self, frame: Frame, type: str = "Path") -> Frame:  # noqa: A002
         from ..explain_more import predict_leaf_node_assignment

@@ -128,6 +128,8 @@ EXPLAIN_SIGS = {
     "h2omx_tree_shap": "PLLIPIPPIPPS",
     # X, ld, n, F, B, ldb, nb, leaves, nleaves, elems, wtab, maxm, sets, bmask, chunk, slabs, out
     "h2omx_tree_shap_background": "PLLIPLIPIPPIPPIPPS",
+    # X, ld, n, F, k, v0 .. v5, hdr, w, nleaves, chunk, slabs, out
+    "h2omx_friedman_h_pd": "PLLIIIIIIIIPPIIPPS",
 }
 
 P2P_SIGS = {

@@ -220,6 +220,13 @@ def op_partial_dependence(cl, model, frame, cols, nbins=20, targets=(None,)):
     return [partial_dependence(m, fr, c, nbins=nbins, target=t, comm=comm) for c in cols for t in targets]
 
 
+def op_friedman_h(cl, model, frame, variables):
+    from ..explain import friedman_h
+
+    comm = cl.comm if cl.world_size > 1 else None
+    return friedman_h(_model(model), _frame(frame), list(variables), comm=comm)
+
+
 def op_model_metrics(cl, model, frame):
     m = _model(model)
     fr = _frame(frame)
