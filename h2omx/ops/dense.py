@@ -42,6 +42,9 @@ KM_MFMA = True
 KM_WAVE = True
 KM_WAVE_CUS = 256
 KM_MFMA_WGS = 512
+# _kmeans_large row chunks: at most KM_LARGE_ELEMS elements per [k | d][m] buffer, at least KM_LARGE_MIN_ROWS rows
+KM_LARGE_ELEMS = 1 << 27
+KM_LARGE_MIN_ROWS = 4096
 
 FAMILIES = {"gaussian": 0, "binomial": 1, "poisson": 2, "gamma": 3, "tweedie": 4, "multinomial": 5,
             "quasibinomial": 6, "fractionalbinomial": 6, "negativebinomial": 7}
@@ -314,7 +317,7 @@ def _kmeans_large(X: torch.Tensor, C: torch.Tensor):
     Cc = C.float().contiguous()
     cn = (Cc.double() ** 2).sum(1).float().contiguous()
     # chunk so G / OH ([k][m]) and Xc ([d][m]) stay within ~1.5 GB of the 288 GB HBM
-    m_chunk = int(max(4096, min(n, (1 << 27) // max(k, d))))
+    m_chunk = int(max(KM_LARGE_MIN_ROWS, min(n, KM_LARGE_ELEMS // max(k, d))))
     nchunks = -(-n // m_chunk)
     assign = torch.empty((n,), dtype=torch.int32, device=dev)
     n_blk = 256

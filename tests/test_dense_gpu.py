@@ -3,9 +3,25 @@ import numpy as np
 import pytest
 import torch
 
+import kmref as KR
 from h2omx.backend import dense as D
 
 pytestmark = pytest.mark.gpu
+
+
+def _kmeans_pass_checks(X, C, ag, sg, cg, eg, sums_tol, sse_tol):
+    """What a Lloyd pass must satisfy whether or not a near-tie flipped against
+    the float64 oracle (tests/kmref.py): at most 0.1 % of the rows flip, each
+    within kmref.flip_bound; the counts are those of the GPU's own assignment;
+    sums and SSE match the float64 statistics of that assignment."""
+    a = ag.cpu().numpy()
+    rows, ok = KR.flips(X, C, a)
+    assert len(rows) <= len(a) // 1000, len(rows)
+    assert ok.all(), (rows[~ok][:5].tolist(), len(rows))
+    assert np.array_equal(cg, np.bincount(a, minlength=C.shape[0]))
+    sr, _, er = KR.given(X, C, a)
+    np.testing.assert_allclose(sg, sr, **sums_tol)
+    np.testing.assert_allclose(eg, er, **sse_tol)
 
 
 @pytest.fixture(autouse=True)
@@ -134,10 +150,7 @@ def test_kmeans_step_matches_reference(cuda_dev, d, k):
     ag, sg, cg, eg = D.kmeans_step(torch.from_numpy(X).to(cuda_dev), torch.from_numpy(C).to(cuda_dev))
     agree = (ag.cpu().numpy() == ar.numpy()).mean()
     assert agree > 0.999  # fp32 near-ties may flip
-    if agree == 1.0:
-        np.testing.assert_allclose(cg, cr)
-        np.testing.assert_allclose(sg, sr, rtol=1e-4, atol=1e-3)
-        np.testing.assert_allclose(eg, er, rtol=1e-3)
+    _kmeans_pass_checks(X, C, ag, sg, cg, eg, dict(rtol=1e-4, atol=1e-3), dict(rtol=1e-3))
 
 
 @pytest.mark.parametrize("mfma", [True, False])
@@ -173,10 +186,7 @@ def test_kmeans_wave_kernel_matches_reference(cuda_dev, monkeypatch, d, k, mfma)
     agree = (ag.cpu().numpy() == ar.numpy()).mean()
     assert agree > 0.999
     assert cg[-1] == 0 and cg.sum() == n
-    if agree == 1.0:
-        np.testing.assert_array_equal(cg, cr)
-        np.testing.assert_allclose(sg, sr, rtol=1e-4, atol=2e-3)
-        np.testing.assert_allclose(eg, er, rtol=1e-4)
+    _kmeans_pass_checks(X, C, ag, sg, cg, eg, dict(rtol=1e-4, atol=2e-3), dict(rtol=1e-4))
     # same assignment as the tile kernel up to fp32 near-ties
     assert (outs[False][0].cpu().numpy() == ag.cpu().numpy()).mean() > 0.999
 
