@@ -788,14 +788,39 @@ class H2OApi:
         m = self._get_model(mid)
         if not isinstance(DKV.get(fid), Frame):
             raise KeyError(fid)
-        cols = parse_list(params.get("cols")) or list(m.x)
+        pairs = [[str(c) for c in p] for p in parse_list(params.get("col_pairs_2dpdp"))]
+        if any(len(p) != 2 for p in pairs):
+            raise ApiError(400, "col_pairs_2dpdp takes a list of column pairs")
+        # as in H2O, pairs without cols compute the pairs alone
+        cols = parse_list(params.get("cols")) or ([] if pairs else list(m.x))
         nbins = int(params.get("nbins", 20))
         targets = parse_list(params.get("targets")) or [None]
+        weight = params.get("weight_column")
+        weight = None if weight in (None, "", "null") else str(weight).strip('"')
+        widx = int(coerce(params.get("weight_column_index", -1), -1))
+        if weight is None and widx >= 0:
+            names = DKV.get(fid).names
+            if widx >= len(names):
+                raise ApiError(400, f"weight_column_index {widx} is outside the frame's {len(names)} columns")
+            weight = names[widx]
+        include_na = bool(coerce(params.get("add_missing_na", False), False))
+        row_index = int(coerce(params.get("row_index", -1), -1))
+        # H2O flattens the per-column grids: user_cols, all their values in order, and how many each has
+        ucols = [str(c) for c in parse_list(params.get("user_cols"))]
+        uvals = [float(a) for a in parse_list(params.get("user_splits"))]
+        unum = [int(a) for a in parse_list(params.get("num_user_splits"))]
+        if len(unum) != len(ucols) or sum(unum) != len(uvals):
+            raise ApiError(400, "user_cols, user_splits and num_user_splits do not agree")
+        user_splits, at = {}, 0
+        for c, k in zip(ucols, unum):
+            user_splits[c] = uvals[at: at + k]
+            at += k
         dest = params.get("destination_key") or f"PartialDependence_{uuid.uuid4().hex[:10]}"
 
         def work(job):
             res = self.cluster.run("partial_dependence", model=m.model_id, frame=fid, cols=cols, nbins=nbins,
-                                   targets=targets)
+                                   targets=targets, col_pairs=pairs, weight_column=weight, include_na=include_na,
+                                   row_index=row_index, user_splits=user_splits)
             self.pdp_results[dest] = res
             return res
 
@@ -810,9 +835,18 @@ class H2OApi:
         if res is None:
             raise KeyError(pid)
         tables = []
+        stats = ["mean_response", "stddev_response", "std_error_mean_response"]
         for r in res:
+            if "columns" in r:
+                a, b = r["columns"]
+                names = [a, b] + stats
+                kinds = ["string" if r["data"] and isinstance(r["data"][0][c], str) else "double" for c in (a, b)]
+                tables.append(S.two_dim_table(f"2D-PartialDependence: {a} and {b}"
+                                              + (f" class {r['target']}" if r["target"] else ""), names,
+                                              kinds + ["double"] * 3, [[d[c] for c in names] for d in r["data"]]))
+                continue
             col = r["column"]
-            names = [col, "mean_response", "stddev_response", "std_error_mean_response"]
+            names = [col] + stats
             tables.append(S.two_dim_table(f"PartialDependence: {col}" + (f" class {r['target']}" if r["target"]
                                                                          else ""), names,
                                           ["string" if isinstance(r["data"][0][col], str) else "double"]

@@ -169,10 +169,27 @@ class H2OConnection:
         r = self.request(f"POST /3/Predictions/models/{model_id}/frames/{frame}", data)
         return r["predictions_frame"]["name"]
 
-    def partial_dependence(self, model_id: str, frame: str, cols=None, nbins: int = 20) -> list:
+    def partial_dependence(self, model_id: str, frame: str, cols=None, nbins: int = 20, *, col_pairs_2dpdp=None,
+                           weight_column: str | None = None, include_na: bool = False, row_index: int = -1,
+                           user_splits: dict | None = None) -> list:
+        """Partial dependence tables: 1-D for ``cols`` (every predictor when neither cols nor pairs are
+        given), then a 5-column 2-D table per pair of ``col_pairs_2dpdp``; ``user_splits`` maps a numeric
+        column to its grid values."""
         data = {"model_id": model_id, "frame_id": frame, "nbins": nbins}
         if cols:
             data["cols"] = list(cols)
+        if col_pairs_2dpdp:
+            data["col_pairs_2dpdp"] = [list(p) for p in col_pairs_2dpdp]
+        if weight_column is not None:
+            data["weight_column"] = weight_column
+        if include_na:
+            data["add_missing_na"] = True
+        if row_index >= 0:
+            data["row_index"] = row_index
+        if user_splits:
+            data["user_cols"] = list(user_splits)
+            data["user_splits"] = [float(a) for v in user_splits.values() for a in v]
+            data["num_user_splits"] = [len(v) for v in user_splits.values()]
         r = self.request("POST /3/PartialDependence/", data)
         self.wait_job(r["job"])
         return self.request(f"GET /3/PartialDependence/{r['destination_key']['name']}")["partial_dependence_data"]

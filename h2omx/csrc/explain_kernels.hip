@@ -463,3 +463,137 @@ H2OMX_API int h2omx_friedman_h_pd(const float* X, int64_t ld, int64_t n, int F, 
                        len, out);
   return launch_status();
 }
+
+// ---------------------------------------------------------------------------
+// Partial dependence: every grid cell of a swept feature in one ensemble walk
+// ---------------------------------------------------------------------------
+// out[y][c][cls][r] is the raw margin of row r with feature fs set to grid[c]
+// (and, for ff >= 0, feature ff set to fixed[y]): what predict_raw_kernel
+// (tree_kernels.hip) gives on the matrix with those rows overwritten, with the
+// same fp32 additions in the same tree order, so the two are bit-identical.
+// The caller initialises out as raw_margin does (init_f or zero).
+//
+// A row that reaches a leaf without meeting a split on fs reaches it for every
+// cell, and a numeric split on fs cuts the ascending grid in two runs.  One
+// thread per row walks each tree once per run: from the root for the first cell
+// c0 of the run, lowering `next` (the first cell after c0 that would leave the
+// path) at every split on fs where c0 goes left, to the upper bound of thr in
+// the grid; cells that go right stay right for the rest of the grid.  The upper
+// bound depends on the node and the grid alone, so the host gives it per node
+// (ub, aligned with nodes).  The leaf value goes to cells [c0, next).  Cells
+// [gn, G) hold NaN and are runs of their own, as is a cell at a categorical
+// group split on fs; a walk that meets no split on fs ends the tree for every
+// cell that is left, NaN cells included.  No stack, no scratch.
+//
+// The cell accumulators live in LDS as [cell][thread] (a lane keeps its bank),
+// at most 64 cells (64 KiB) per window of sorted cells; a window starts its
+// walk at its first cell and clips runs at its end.  blockIdx.z = window * K +
+// class, blockIdx.y = y.
+namespace {
+
+constexpr int kPdWindow = 64;
+
+struct PdNode {  // TreeNode of tree_kernels.hip (32 B)
+  int feat, bin, left, na_left;
+  float thr, value, gain, weight;
+};
+
+template <bool COUNT>
+__global__ __launch_bounds__(256) void pd_sweep_kernel(const float* __restrict__ X, int64_t ld, int64_t n,
+                                                       const PdNode* __restrict__ nodes,
+                                                       const int* __restrict__ roots, int ntrees, int K,
+                                                       const uint32_t* __restrict__ catbits, int fs,
+                                                       const float* __restrict__ grid, const int* __restrict__ ub,
+                                                       int G, int gn, int ff, const float* __restrict__ fixed,
+                                                       float* __restrict__ out,
+                                                       unsigned long long* __restrict__ walks) {
+  extern __shared__ float acc[];  // [W][256]
+  const int tid = threadIdx.x;
+  const int64_t r = (int64_t)blockIdx.x * 256 + tid;
+  if (r >= n) return;
+  const int cls = (int)blockIdx.z % K;
+  const int w0 = ((int)blockIdx.z / K) * kPdWindow;
+  const int w1 = w0 + kPdWindow < G ? w0 + kPdWindow : G;
+  const int W = w1 - w0;
+  // cells [w0, wn) of the window are ascending numbers, [wn, w1) are NaN
+  const int wn = gn < w0 ? w0 : (gn < w1 ? gn : w1);
+  const float fy = ff >= 0 ? fixed[blockIdx.y] : 0.0f;
+  float* __restrict__ o = out + (((int64_t)blockIdx.y * G + w0) * K + cls) * n + r;
+  for (int c = 0; c < W; ++c) acc[c * 256 + tid] = o[(int64_t)c * K * n];
+  unsigned cnt = 0;
+  for (int t = cls; t < ntrees; t += K) {
+    const int root = roots[t];
+    const PdNode* __restrict__ tr = nodes + root;
+    int c0 = w0;
+    while (c0 < w1) {
+      const float gv = grid[c0];
+      int next = c0 < wn ? wn : c0 + 1;
+      bool met = false;  // a split on fs on this walk's path
+      int id = 0;
+      for (int guard = 0; guard < 64; ++guard) {
+        const PdNode nd = tr[id];
+        if (nd.feat < 0) break;
+        const bool swept = nd.feat == fs;
+        met |= swept;
+        const float v = swept ? gv : (nd.feat == ff ? fy : X[(int64_t)nd.feat * ld + r]);
+        bool left;
+        if (v != v) {
+          left = (nd.na_left & 1) != 0;
+        } else if (nd.na_left & 2) {
+          const int b = (int)v;
+          const uint32_t* __restrict__ bits = catbits + 8 * ((int64_t)root + id);
+          left = (b < 0 || b > 255) ? (nd.na_left & 1) != 0 : ((bits[b >> 5] >> (b & 31)) & 1u) != 0;
+          if (swept) next = c0 + 1;
+        } else {
+          left = v <= nd.thr;
+          if (swept && left) {
+            // grid[c0] <= thr, so the bound lies past c0; clamped all the same, a run never ends before c0 + 1
+            int u = ub[root + id];
+            u = u > c0 ? u : c0 + 1;
+            next = u < next ? u : next;
+          }
+        }
+        id = left ? nd.left : nd.left + 1;
+      }
+      const float val = tr[id].value;
+      if (!met) next = w1;  // the path never asked for the swept value: every cell left ends here
+      for (int c = c0; c < next; ++c) acc[(c - w0) * 256 + tid] += val;
+      c0 = next;
+      if (COUNT) ++cnt;
+    }
+  }
+  for (int c = 0; c < W; ++c) o[(int64_t)c * K * n] = acc[c * 256 + tid];
+  if (COUNT) atomicAdd(walks, (unsigned long long)cnt);
+}
+
+}  // namespace
+
+// Margins of n rows for G cells of feature fs: grid [G] holds gn ascending
+// numbers, then G - gn NaNs; ub [total nodes] is, for a node that splits on fs,
+// the number of the gn cells that are <= its thr.  ff >= 0 pins feature ff to
+// fixed[y] for each of the ny slices of out [ny][G][K][n] (ff < 0: ny = 1, fixed
+// unused).  nodes, roots and catbits are those of h2omx_predict_raw.  walks
+// (optional) receives the number of root-to-leaf walks made; it selects a
+// separate instantiation, the kernel without it carries no counter.
+H2OMX_API int h2omx_pd_sweep(const float* X, int64_t ld, int64_t n, int F, const void* nodes, const int* roots,
+                             int ntrees, int K, const uint32_t* catbits, int fs, const float* grid, const int* ub,
+                             int G, int gn, int ff, const float* fixed, int ny, float* out,
+                             unsigned long long* walks, hipStream_t stream) {
+  if (n <= 0 || G <= 0) return kOk;
+  if (K < 1 || ntrees < 0 || fs < 0 || fs >= F || ff >= F || ff == fs || gn < 0 || gn > G || ny < 1 || ld < n)
+    return kBadArg;
+  if (ff >= 0 ? fixed == nullptr : ny != 1) return kBadArg;
+  const int64_t gx = (n + 255) / 256;
+  const int64_t gz = (int64_t)((G + kPdWindow - 1) / kPdWindow) * K;
+  if (gx > 0x7FFFFFFF || ny > 65535 || gz > 65535) return kBadArg;
+  const size_t shm = (size_t)(G < kPdWindow ? G : kPdWindow) * 256 * sizeof(float);
+  const dim3 blocks((unsigned)gx, (unsigned)ny, (unsigned)gz);
+  const PdNode* nd = reinterpret_cast<const PdNode*>(nodes);
+  if (walks != nullptr)
+    hipLaunchKernelGGL((pd_sweep_kernel<true>), blocks, dim3(256), shm, stream, X, ld, n, nd, roots, ntrees, K,
+                       catbits, fs, grid, ub, G, gn, ff, fixed, out, walks);
+  else
+    hipLaunchKernelGGL((pd_sweep_kernel<false>), blocks, dim3(256), shm, stream, X, ld, n, nd, roots, ntrees, K,
+                       catbits, fs, grid, ub, G, gn, ff, fixed, out, walks);
+  return launch_status();
+}

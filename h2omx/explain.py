@@ -19,7 +19,12 @@ over the same path table in float64 (friedman_h_pd_kernel on the GPU).
 ``partial_dependence(model, frame, col, nbins)`` (H2O PartialDependence):
 mean / sd / standard error of the model response with ``col`` forced to
 each grid value (``nbins`` equally spaced values between the column's min
-and max, every level for categorical columns), scored on the device.
+and max, every level for categorical columns), scored on the device; with
+``col2`` the 2-D table of a pair, with ``weight_column`` / ``include_na`` /
+``row_index`` H2O's options of the same names.  Tree models on a device frame
+get every cell's margins from one pass of pd_sweep_kernel
+(csrc/explain_kernels.hip), bit-identical to scoring the frame with the
+columns overwritten; every other model and frame takes that loop.
 """
 from __future__ import annotations
 
@@ -561,17 +566,131 @@ def _response(model, P: torch.Tensor, target: str | None) -> torch.Tensor:
     return P[0]
 
 
-def partial_dependence(model, frame: Frame, col: str, nbins: int = 20, target: str | None = None,
-                       user_splits=None, comm=None) -> dict:
-    """H2O PartialDependence for one column: {col, mean_response,
-    stddev_response, std_error_mean_response} per grid value."""
-    frame = model.adapt_frame(frame)
+NA_LABEL = ".missing(NA)"
+_PD_TREE_ALGOS = ("gbm", "drf", "xgboost", "generic")
+
+
+def _pd_sorted(grid):
+    """(cells ascending with the NaN cells last, the sorting permutation, the
+    number of non-NaN cells) of a grid of float32 cell values."""
+    g = np.asarray(grid, np.float32).reshape(-1)
+    order = np.argsort(g, kind="stable")
+    gs = np.ascontiguousarray(g[order])
+    return gs, order, int((~np.isnan(gs)).sum())
+
+
+def _pd_margin_chunks(model, X: torch.Tensor, fs: int, grid, ff: int | None = None, fixed=None, *,
+                      budget: int | None = None, walks: torch.Tensor | None = None):
+    """The HIP path (csrc/explain_kernels.hip pd_sweep_kernel): yields (r0, r1,
+    margins [NY][G][K][r1 - r0]) over row ranges of the device matrix X [F][n],
+    each margin buffer (and its copy in the caller's cell order, where the grid
+    was not ascending) within ``budget`` bytes, half of the free device memory
+    by default.  Cell g of slice y is ``ens.raw_margin`` of X with row ``fs``
+    set to grid[g] and row ``ff`` to fixed[y], bit for bit.  ``walks`` (int64
+    [1] on the device) is a debug output: the root-to-leaf walks made."""
+    from .ops import P, check, explain_lib, stream
+
+    ens = model.ens
+    F, n = (int(a) for a in X.shape)
+    dev = X.device
+    gs, order, gn = _pd_sorted(grid)
+    G = int(gs.shape[0])
+    fx = None if ff is None else np.ascontiguousarray(np.asarray(fixed, np.float32).reshape(-1))
+    NY = 1 if fx is None else int(fx.shape[0])
+    K, nt = int(ens.K), int(ens.ntrees)
+    T = nt * K
+    if not 0 <= fs < F or (ff is not None and (not 0 <= ff < F or ff == fs)):
+        raise ValueError(f"swept feature {fs} and fixed feature {ff} must be two different rows of the {F}-row matrix")
+    if NY > 65535 or -(-G // 64) * K > 65535:
+        raise ValueError(f"a partial dependence table of {NY} x {G} cells and {K} classes exceeds the launch grid")
+    permuted = not np.array_equal(order, np.arange(G))
+    per_row = 4 * NY * G * K * (2 if permuted else 1)
+    if budget is None:
+        budget = torch.cuda.mem_get_info(dev)[0] // 2
+    rows = int(budget) // max(per_row, 1)
+    if rows < 1:
+        raise ValueError(f"the partial dependence margins of one row ({NY} x {G} cells, {K} classes) need {per_row} "
+                         f"bytes; the limit is {int(budget)} bytes: use a smaller grid")
+    rows = min(rows, 1 << 30)
+    if G == 0 or NY == 0 or n == 0:
+        yield 0, n, torch.empty((NY, G, K, n), dtype=torch.float32, device=dev)
+        return
+    Xc = X.float().contiguous()
+    nodes, cbits, roots = ens.device_nodes(dev, T)
+    # per node: how many of the ascending cells are <= thr (read at the nodes that split on fs)
+    thr = np.ascontiguousarray(ens.trees[:T]["thr"]).reshape(-1)
+    ub = torch.from_numpy(np.searchsorted(gs[:gn], thr, side="right").astype(np.int32)).to(dev)
+    gd = torch.from_numpy(gs).to(dev)
+    fd = None if fx is None else torch.from_numpy(fx).to(dev)
+    init = None if ens.average else torch.from_numpy(ens.init_f.astype(np.float32)).to(dev)
+    inv = torch.from_numpy(np.argsort(order)).to(dev) if permuted else None
+    for r0 in range(0, n, rows):
+        nc = min(rows, n - r0)
+        out = torch.empty((NY, G, K, nc), dtype=torch.float32, device=dev)
+        if ens.average:
+            out.zero_()
+        else:
+            out.copy_(init[None, None, :, None].expand(NY, G, K, nc))
+        if T:
+            Xv = Xc[:, r0: r0 + nc]
+            check(explain_lib().h2omx_pd_sweep(P(Xv), max(int(Xc.stride(0)), nc), nc, F, P(nodes), P(roots), T, K,
+                                               P(cbits), fs, P(gd), P(ub), G, gn, -1 if ff is None else ff, P(fd), NY,
+                                               P(out), P(walks), stream(dev)), "pd_sweep")
+        if ens.average and nt > 0:
+            out /= nt
+        yield r0, r0 + nc, (out if inv is None else out.index_select(1, inv))
+
+
+def _pd_margins_device(model, X: torch.Tensor, fs: int, grid, ff: int | None = None, fixed=None, *,
+                       budget: int | None = None, walks: torch.Tensor | None = None) -> torch.Tensor:
+    """Margins [NY][G][K][n] of every (fixed value, grid cell) by the sweep
+    kernel; see :func:`_pd_margin_chunks`."""
+    parts = [M for _, _, M in _pd_margin_chunks(model, X, fs, grid, ff, fixed, budget=budget, walks=walks)]
+    return parts[0] if len(parts) == 1 else torch.cat(parts, 3)
+
+
+def _pd_margins_loop(model, X: torch.Tensor, fs: int, grid, ff: int | None = None, fixed=None) -> torch.Tensor:
+    """The oracle of :func:`_pd_margins_device`: the rows of the matrix
+    overwritten and one ``ens.raw_margin`` call per cell (CPU or device X)."""
+    ens = model.ens
+    Xw = X.float().clone()
+    g = np.asarray(grid, np.float32).reshape(-1)
+    fx = [None] if ff is None else list(np.asarray(fixed, np.float32).reshape(-1))
+    out = torch.empty((len(fx), len(g), int(ens.K), int(X.shape[1])), dtype=torch.float32, device=X.device)
+    for y, fv in enumerate(fx):
+        if ff is not None:
+            Xw[ff] = float(fv)
+        for c, gv in enumerate(g):
+            Xw[fs] = float(gv)
+            out[y, c] = ens.raw_margin(Xw)
+    return out
+
+
+def _pd_device_matrix(model, frame: Frame, cols) -> torch.Tensor | None:
+    """The model's feature matrix of the adapted ``frame`` when the sweep kernel
+    can answer for ``cols``: a tree ensemble scored by ``TreeModel.predict_raw``
+    alone on a device matrix of which every column of ``cols`` is a row."""
+    from .models.tree_models import TreeModel
+
+    if getattr(model, "ens", None) is None or model.algo not in _PD_TREE_ALGOS or not isinstance(model, TreeModel):
+        return None
+    if type(model).predict_raw is not TreeModel.predict_raw or model.preprocessors or model.cat_encoder is not None:
+        return None
+    if any(c not in model.x for c in cols) or any(c not in frame.names for c in model.x):
+        return None
+    X = frame.feature_matrix(model.x)
+    return X if X.is_cuda else None
+
+
+def _pd_grid(model, frame: Frame, col: str, nbins: int, user_splits, include_na: bool, comm):
+    """(cell values, labels) of one column: every level code of a categorical
+    column, else ``user_splits`` or ``nbins`` equally spaced values over the
+    column's global min .. max; with ``include_na`` one NA cell comes last."""
     v = frame.vec(col)
-    n = frame.nrows
     if v.vtype == ENUM:
         dom = list(model.feature_domains.get(col) or v.domain or [])
         grid = list(range(len(dom)))
-        labels = dom
+        labels = list(dom)
     else:
         if user_splits is not None:
             grid = [float(a) for a in user_splits]
@@ -585,21 +704,143 @@ def partial_dependence(model, frame: Frame, col: str, nbins: int = 20, target: s
                 comm.all_reduce_(mm, "min")
             lo_v, hi_v = float(mm[0]), float(-mm[1])
             grid = list(np.linspace(lo_v, hi_v, nbins)) if hi_v > lo_v else [lo_v]
-        labels = grid
-    rows = []
-    for g in grid:
-        if v.vtype == ENUM:
-            nv = Vec(col, torch.full((n,), int(g), dtype=torch.int32, device=v.data.device), ENUM, list(dom))
+        labels = list(grid)
+    if include_na:
+        grid = grid + [float("nan")]
+        labels = labels + [NA_LABEL if v.vtype == ENUM else float("nan")]
+    return grid, labels
+
+
+def _pd_vec(model, v: Vec, g, n: int) -> Vec:
+    """Column ``v`` forced to the cell value ``g`` (NaN: NA) on ``n`` rows."""
+    if v.vtype == ENUM:
+        code = -1 if g != g else int(g)
+        dom = list(model.feature_domains.get(v.name) or v.domain or [])
+        return Vec(v.name, torch.full((n,), code, dtype=torch.int32, device=v.data.device), ENUM, dom)
+    return Vec(v.name, torch.full((n,), float(g), dtype=torch.float32, device=v.data.device), v.vtype)
+
+
+def _pd_responses_loop(model, frame: Frame, cols, grids, target):
+    """The general path: per cell (the first column slowest) the response of
+    ``model.predict_raw`` on the frame with the columns overwritten."""
+    n = frame.nrows
+    for g0 in grids[0]:
+        v0 = _pd_vec(model, frame.vec(cols[0]), g0, n)
+        for g1 in (grids[1] if len(cols) > 1 else [None]):
+            repl = {cols[0]: v0}
+            if len(cols) > 1:
+                repl[cols[1]] = _pd_vec(model, frame.vec(cols[1]), g1, n)
+            fr = Frame([repl.get(u.name, u) for u in frame.vecs])
+            yield _response(model, model.predict_raw(fr), target).double()
+
+
+def _pd_responses_device(model, frame: Frame, X: torch.Tensor, target, r0: int, r1: int, M):
+    """The responses of one row range from its margins M [NY][G][K][rows]: the
+    tail of ``TreeModel.predict_raw`` per cell."""
+    off = None
+    if model.params.get("offset_column"):
+        off = frame.vec(model.params["offset_column"]).as_float()[r0:r1]
+    for y in range(M.shape[0]):
+        for c in range(M.shape[1]):
+            yield _response(model, model.scores_from_margin(M[y, c], off, X.device), target).double()
+
+
+def _pd_moments(responses, w) -> torch.Tensor | None:
+    """[cells][2] float64 = {sum(w r), sum(w r^2)} of the cells' responses."""
+    pairs = []
+    for r in responses:
+        wr = r if w is None else w.to(r.device) * r
+        pairs.append(torch.stack([wr.sum(), (wr * r).sum()]))
+    return torch.stack(pairs) if pairs else None
+
+
+def partial_dependence(model, frame: Frame, col: str, nbins: int = 20, target: str | None = None,
+                       user_splits=None, comm=None, *, col2: str | None = None, user_splits2=None,
+                       weight_column: str | None = None, include_na: bool = False, row_index: int = -1) -> dict:
+    """H2O PartialDependence for one column: {col, mean_response,
+    stddev_response, std_error_mean_response} per grid value, or with ``col2``
+    for the pair (``col`` varies slowest; each column keeps its 1-D grid).
+    ``weight_column`` weights the rows (NaN or <= 0: left out), ``include_na``
+    adds one NA cell per column, ``row_index >= 0`` gives the table of that one
+    row of the whole frame.  Tree models on a device frame take the sweep
+    kernel; everything else overwrites the columns and scores every cell."""
+    cols = [col] if col2 is None else [col, col2]
+    if col2 is not None and col2 == col:
+        raise ValueError(f"a 2-D partial dependence pair names column {col!r} twice")
+    for c in cols:
+        if c not in frame.names:
+            raise ValueError(f"partial dependence column {c!r} is not in the frame")
+        if c == model.y:
+            raise ValueError(f"partial dependence column {c!r} is the response column")
+    if weight_column is not None:
+        if weight_column in cols:
+            raise ValueError(f"weight column {weight_column!r} is a partial dependence column")
+        if weight_column not in frame.names:
+            raise ValueError(f"weight column {weight_column!r} is not in the frame")
+    frame = model.adapt_frame(frame)
+    n = frame.nrows
+    splits = [user_splits, user_splits2]
+    grids, labels = zip(*[_pd_grid(model, frame, c, nbins, splits[j], include_na, comm) for j, c in enumerate(cols)])
+    ncells = len(grids[0]) * (len(grids[1]) if len(cols) > 1 else 1)
+    multi = comm is not None and comm.world_size > 1
+    dev = frame.device
+    single = row_index is not None and int(row_index) >= 0
+    w = None
+    if single:
+        # the index counts rows of the whole frame: the owning shard alone contributes
+        counts = [n]
+        if multi:
+            counts = [int(a) for a in comm.all_gather_cat(torch.tensor([n], dtype=torch.int64, device=dev)).tolist()]
+        if int(row_index) >= sum(counts):
+            raise ValueError(f"row_index {int(row_index)} is outside the frame of {sum(counts)} rows")
+        local = int(row_index) - (sum(counts[:comm.rank]) if multi else 0)
+        own = 0 <= local < n
+        if own:
+            frame = frame.rows(torch.tensor([local], dtype=torch.int64))
+        sw = m = 1.0 if own else 0.0
+    elif weight_column is not None:
+        wv = frame.vec(weight_column).as_float().double()
+        keep = ~torch.isnan(wv) & (wv > 0)
+        w = torch.where(keep, wv, torch.zeros_like(wv))
+        sw, m = float(w.sum()), float(keep.sum())
+    else:
+        sw = m = float(n)
+    mom = None
+    if not single or own:
+        X = _pd_device_matrix(model, frame, cols)
+        if X is not None:
+            # sweep the last column; a pair pins the first one per slice
+            ix = [model.x.index(c) for c in cols]
+            g32 = [np.asarray(g, np.float32) for g in grids]
+            chunks = _pd_margin_chunks(model, X, ix[-1], g32[-1], ix[0] if len(cols) > 1 else None,
+                                       g32[0] if len(cols) > 1 else None)
+            for r0, r1, M in chunks:
+                part = _pd_moments(_pd_responses_device(model, frame, X, target, r0, r1, M),
+                                   None if w is None else w[r0:r1])
+                mom = part if mom is None else mom + part
         else:
-            nv = Vec(col, torch.full((n,), float(g), dtype=torch.float32, device=v.data.device), v.vtype)
-        fr = Frame([nv if u.name == col else u for u in frame.vecs])
-        r = _response(model, model.predict_raw(fr), target).double()
-        st = torch.stack([r.sum(), (r * r).sum(), torch.tensor(float(n), dtype=torch.float64, device=r.device)])
-        if comm is not None and comm.world_size > 1:
-            comm.all_reduce_(st)
-        s, s2, cnt = (float(a) for a in st)
-        mean = s / max(cnt, 1.0)
-        sd = math.sqrt(max(s2 / max(cnt, 1.0) - mean * mean, 0.0) * cnt / max(cnt - 1.0, 1.0))
-        rows.append({col: labels[len(rows)], "mean_response": mean, "stddev_response": sd,
-                     "std_error_mean_response": sd / math.sqrt(max(cnt, 1.0))})
-    return {"column": col, "target": target, "data": rows}
+            mom = _pd_moments(_pd_responses_loop(model, frame, cols, grids, target), w)
+    if mom is None:
+        mom = torch.zeros((ncells, 2), dtype=torch.float64, device=dev)
+    # every cell's moments, sum(w) and the rows kept travel in one reduction
+    st = torch.cat([mom.reshape(-1), torch.tensor([sw, m], dtype=torch.float64, device=mom.device)])
+    if multi:
+        comm.all_reduce_(st)
+    st = [float(a) for a in st.cpu()]
+    sw, cnt = st[-2], st[-1]
+    den = sw if sw > 0 else 1.0
+    rows = []
+    for i in range(ncells):
+        s, s2 = st[2 * i], st[2 * i + 1]
+        mean = s / den
+        sd = 0.0 if single else math.sqrt(max(s2 / den - mean * mean, 0.0) * cnt / max(cnt - 1.0, 1.0))
+        se = sd / math.sqrt(max(cnt, 1.0))
+        if len(cols) == 1:
+            row = {col: labels[0][i]}
+        else:
+            row = {col: labels[0][i // len(grids[1])], col2: labels[1][i % len(grids[1])]}
+        row.update(mean_response=mean, stddev_response=sd, std_error_mean_response=se)
+        rows.append(row)
+    if len(cols) == 1:
+        return {"column": col, "target": target, "data": rows}
+    return {"columns": [col, col2], "target": target, "data": rows}

@@ -210,7 +210,7 @@ def glm_contributions(model, frame: Frame, *, background_frame: Frame | None = N
 
 def ice(model, frame: Frame, col: str, nbins: int = 20, target: str | None = None, max_rows: int = 1000) -> dict:
     """Per-row ICE curves for up to ``max_rows`` rows: {grid, curves [rows][grid]}."""
-    from .explain import _response
+    from .explain import _pd_device_matrix, _pd_margins_device, _pd_responses_device, _pd_responses_loop
 
     frame = model.adapt_frame(frame)
     n = min(frame.nrows, int(max_rows))
@@ -226,14 +226,14 @@ def ice(model, frame: Frame, col: str, nbins: int = 20, target: str | None = Non
         lo, hi = (float(x[ok].min()), float(x[ok].max())) if bool(ok.any()) else (0.0, 0.0)
         grid = list(np.linspace(lo, hi, nbins)) if hi > lo else [lo]
         labels = grid
-    curves = []
-    for g in grid:
-        if v.vtype == ENUM:
-            nv = Vec(col, torch.full((n,), int(g), dtype=torch.int32, device=v.data.device), ENUM, list(dom))
-        else:
-            nv = Vec(col, torch.full((n,), float(g), dtype=torch.float32, device=v.data.device), v.vtype)
-        fr = Frame([nv if u.name == col else u for u in sub.vecs])
-        curves.append(_response(model, model.predict_raw(fr), target).double().cpu())
+    X = _pd_device_matrix(model, sub, [col])
+    if X is not None:
+        # every cell's margins from one pass of the sweep kernel; the scores are predict_raw's own tail
+        M = _pd_margins_device(model, X, model.x.index(col), np.asarray(grid, np.float32))
+        responses = _pd_responses_device(model, sub, X, target, 0, n, M)
+    else:
+        responses = _pd_responses_loop(model, sub, [col], [grid], target)
+    curves = [r.cpu() for r in responses]
     C = torch.stack(curves, 1).numpy()
     return {"column": col, "grid": labels, "curves": C.tolist(), "mean": C.mean(0).tolist()}
 

@@ -207,11 +207,27 @@ class Model:
 
         return explain([self], frame, **kw)
 
-    def partial_dependence(self, frame: Frame, cols=None, nbins: int = 20, target=None) -> list[dict]:
+    def partial_dependence(self, frame: Frame, cols=None, nbins: int = 20, target=None, *, col_pairs_2dpdp=None,
+                           weight_column=None, include_na: bool = False, row_index: int = -1,
+                           user_splits=None) -> list[dict]:
+        """H2O ``partial_plot`` data: the 1-D tables of ``cols`` (every predictor when neither ``cols``
+        nor pairs are given), then one 2-D table per pair of ``col_pairs_2dpdp``.  ``user_splits`` maps a
+        numeric column to its grid values (h2omx.explain.partial_dependence)."""
         from ..explain import partial_dependence
 
-        return [partial_dependence(self, frame, c, nbins=nbins, target=target, comm=self.comm)
-                for c in (cols or self.x)]
+        pairs = [tuple(p) for p in (col_pairs_2dpdp or [])]
+        for p in pairs:
+            if len(p) != 2:
+                raise ValueError(f"col_pairs_2dpdp takes pairs of columns, got {list(p)!r}")
+        if cols is None and not pairs:
+            cols = self.x
+        us = dict(user_splits or {})
+        kw = dict(nbins=nbins, target=target, comm=self.comm, weight_column=weight_column, include_na=include_na,
+                  row_index=row_index)
+        out = [partial_dependence(self, frame, c, user_splits=us.get(c), **kw) for c in (cols or [])]
+        out += [partial_dependence(self, frame, a, user_splits=us.get(a), col2=b, user_splits2=us.get(b), **kw)
+                for a, b in pairs]
+        return out
 
     def summary(self) -> dict:
         return {"model_id": self.model_id, "algo": self.algo, "category": self.category}

@@ -90,6 +90,23 @@ class TreeEnsemble:
         return out
 
     # -- scoring ---------------------------------------------------------------
+    def device_nodes(self, dev, T: int):
+        """The first ``T`` trees as the scoring kernels read them, cached on the
+        ensemble: (node records as bytes, categorical bitsets or None, roots)."""
+        key = (T, str(dev), self.trees.shape, id(self.trees), id(self.catbits))
+        cache = getattr(self, "_dev_nodes", None)
+        if cache is not None and cache[0] == key:
+            nodes, cbits = cache[1], cache[2]
+        else:
+            nodes = torch.from_numpy(self.trees[:T].reshape(-1).view(np.uint8).copy()).to(dev)
+            cbits = None
+            if self.catbits is not None:
+                cb = np.ascontiguousarray(self.catbits[:T], np.uint32).reshape(-1)
+                cbits = torch.from_numpy(cb.view(np.int32).copy()).to(dev)
+            self._dev_nodes = (key, nodes, cbits)
+        roots = torch.arange(T, dtype=torch.int32, device=dev) * self.trees.shape[1]
+        return nodes, cbits, roots
+
     def raw_margin(self, X: torch.Tensor, ntrees: int | None = None) -> torch.Tensor:
         """Margins [K][n] for feature-major raw data X [F][n]."""
         nt = self.ntrees if ntrees is None else ntrees
@@ -98,19 +115,7 @@ class TreeEnsemble:
         if X.is_cuda:
             dev = X.device
             Xc = X.float().contiguous()
-            key = (T, str(dev), self.trees.shape, id(self.trees), id(self.catbits))
-            cache = getattr(self, "_dev_nodes", None)
-            if cache is not None and cache[0] == key:
-                nodes, cbits = cache[1], cache[2]
-            else:
-                nodes = torch.from_numpy(self.trees[:T].reshape(-1).view(np.uint8).copy()).to(dev)
-                cbits = None
-                if self.catbits is not None:
-                    cb = np.ascontiguousarray(self.catbits[:T], np.uint32).reshape(-1)
-                    cbits = torch.from_numpy(cb.view(np.int32).copy()).to(dev)
-                self._dev_nodes = (key, nodes, cbits)
-            cap = self.trees.shape[1]
-            roots = torch.arange(T, dtype=torch.int32, device=dev) * cap
+            nodes, cbits, roots = self.device_nodes(dev, T)
             out = torch.empty((self.K, n), dtype=torch.float32, device=dev)
             if self.average:
                 out.zero_()

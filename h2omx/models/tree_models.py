@@ -53,9 +53,15 @@ class TreeModel(Model):
         X = frame.feature_matrix(self.x)
         dev = X.device
         m = self.ens.raw_margin(X)
-        if self.params.get("offset_column"):
-            m = m + frame.vec(self.params["offset_column"]).as_float()[None, :].to(m.device)
-        P = self._link(m.to(dev))
+        off = frame.vec(self.params["offset_column"]).as_float() if self.params.get("offset_column") else None
+        return self.scores_from_margin(m, off, dev)
+
+    def scores_from_margin(self, m: torch.Tensor, offset: torch.Tensor | None = None, dev=None) -> torch.Tensor:
+        """The tail of ``predict_raw``: margins [K][n] of the ensemble (plus the
+        rows' ``offset``) through the link and the class-balance correction."""
+        if offset is not None:
+            m = m + offset[None, :].to(m.device)
+        P = self._link(m if dev is None else m.to(dev))
         cd = getattr(self, "class_dist", None)
         return P if cd is None else correct_probabilities(P, *cd)
 

@@ -130,6 +130,8 @@ EXPLAIN_SIGS = {
     "h2omx_tree_shap_background": "PLLIPLIPIPPIPPIPPS",
     # X, ld, n, F, k, v0 .. v5, hdr, w, nleaves, chunk, slabs, out
     "h2omx_friedman_h_pd": "PLLIIIIIIIIPPIIPPS",
+    # X, ld, n, F, nodes, roots, ntrees, K, catbits, fs, grid, ub, G, gn, ff, fixed, ny, out, walks
+    "h2omx_pd_sweep": "PLLIPPIIPIPPIIIPIPPS",
 }
 
 P2P_SIGS = {

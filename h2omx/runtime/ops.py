@@ -211,13 +211,20 @@ def op_predict(cl, model, frame, dest, kind="predict", leaf_type="Path", backgro
     return {"key": dest, "rows": global_nrows(pf, cl.comm)}
 
 
-def op_partial_dependence(cl, model, frame, cols, nbins=20, targets=(None,)):
+def op_partial_dependence(cl, model, frame, cols, nbins=20, targets=(None,), col_pairs=(), weight_column=None,
+                          include_na=False, row_index=-1, user_splits=None):
     from ..explain import partial_dependence
 
     m = _model(model)
     fr = _frame(frame)
     comm = cl.comm if cl.world_size > 1 else None
-    return [partial_dependence(m, fr, c, nbins=nbins, target=t, comm=comm) for c in cols for t in targets]
+    us = dict(user_splits or {})
+    kw = dict(nbins=nbins, comm=comm, weight_column=weight_column, include_na=bool(include_na),
+              row_index=int(row_index))
+    out = [partial_dependence(m, fr, c, target=t, user_splits=us.get(c), **kw) for c in (cols or []) for t in targets]
+    out += [partial_dependence(m, fr, a, target=t, user_splits=us.get(a), col2=b, user_splits2=us.get(b), **kw)
+            for a, b in (col_pairs or ()) for t in targets]
+    return out
 
 
 def op_friedman_h(cl, model, frame, variables):
