@@ -15,7 +15,7 @@ build models, score and download MOJOs:
   POST /99/Models.bin/{id}   POST /99/Models.upload.bin   GET /99/Models.fetch.bin/{id}
   POST /3/Predictions/models/{m}/frames/{f}   POST /4/Predictions/models/{m}/frames/{f}
   POST /3/ModelMetrics/models/{m}/frames/{f}
-  POST /3/Predictions/...?predict_contributions=true  (TreeSHAP)
+  POST /3/Predictions/...?predict_contributions=true  (TreeSHAP; top_n, bottom_n, compare_abs: ranked)
   POST /3/PartialDependence  GET /3/PartialDependence/{id}
   POST /3/FriedmansPopescusH  (H statistic: model_id, frame, variables)
   POST /99/Grid/{algo}       GET /99/Grids[/{id}]
@@ -739,6 +739,23 @@ class H2OApi:
         dest = params.get("predictions_frame") or f"prediction_{uuid.uuid4().hex[:10]}"
         kind = _predict_kind(params)
         extra = {}
+        # H2O's ranked contributions: top_n, bottom_n, compare_abs, predict_contributions_output_format
+        rank = {}
+        for name in ("top_n", "bottom_n"):
+            raw = str(params.get(name, "") or "").strip('"')
+            if raw:
+                try:
+                    rank[name] = int(raw)
+                except ValueError:
+                    raise ApiError(400, f"{name} must be an integer, got {raw!r}") from None
+        if str(params.get("compare_abs", "false")).lower() == "true":
+            rank["compare_abs"] = True
+        fmt = str(params.get("predict_contributions_output_format") or "").strip('"')
+        if fmt:
+            rank["output_format"] = fmt
+        if rank and kind != "contributions":
+            raise ApiError(400, "top_n, bottom_n, compare_abs and predict_contributions_output_format belong to "
+                                "predict_contributions")
         if kind == "contributions":
             # H2O's baseline SHAP: background_frame (a frame key) and output_per_reference
             if str(params.get("output_space", "false")).lower() == "true":
@@ -749,6 +766,7 @@ class H2OApi:
                 raise KeyError(bg)
             if bg or per_ref:
                 extra = {"background_frame": bg or None, "output_per_reference": per_ref}
+            extra.update(rank)
         self.cluster.run("predict", model=m.model_id, frame=fid, dest=dest, kind=kind,
                          leaf_type=params.get("leaf_node_assignment_type") or "Path", **extra)
         return m, dest

@@ -158,14 +158,25 @@ class H2OConnection:
         return j["dest"]["name"]
 
     def predict_contributions(self, model_id: str, frame: str, background_frame: str | None = None,
-                              output_per_reference: bool = False) -> str:
+                              output_per_reference: bool = False, top_n: int | None = None,
+                              bottom_n: int | None = None, compare_abs: bool = False,
+                              output_format: str | None = None) -> str:
         """SHAP contributions; with ``background_frame`` (a frame key) baseline SHAP against its rows,
-        averaged or (``output_per_reference``) one row per (row, background row)."""
+        averaged or (``output_per_reference``) one row per (row, background row).  ``top_n`` / ``bottom_n``
+        / ``compare_abs`` return per row the strongest features by name and value."""
         data = {"predict_contributions": True}
         if background_frame is not None:
             data["background_frame"] = background_frame
         if output_per_reference:
             data["output_per_reference"] = True
+        if top_n is not None:
+            data["top_n"] = top_n
+        if bottom_n is not None:
+            data["bottom_n"] = bottom_n
+        if compare_abs:
+            data["compare_abs"] = True
+        if output_format is not None:
+            data["predict_contributions_output_format"] = output_format
         r = self.request(f"POST /3/Predictions/models/{model_id}/frames/{frame}", data)
         return r["predictions_frame"]["name"]
 

@@ -597,3 +597,141 @@ H2OMX_API int h2omx_pd_sweep(const float* X, int64_t ld, int64_t n, int F, const
                        catbits, fs, grid, ub, G, gn, ff, fixed, out, walks);
   return launch_status();
 }
+
+// ---------------------------------------------------------------------------
+// Ranked contributions: the top / bottom features of every row (reason codes)
+// ---------------------------------------------------------------------------
+// phi [F][ld] holds a row's contributions down a column.  With key[f] = phi[f]
+// (|phi[f]| for ABS) two total orders are defined, both breaking ties towards
+// the lower feature index (-0.0 == +0.0 is a tie):
+//     descending D: f before g iff key[f] > key[g] or (key[f] == key[g] and f < g),
+//     ascending  A: f before g iff key[f] < key[g] or (key[f] == key[g] and f < g).
+// The position of f in an order is the number of features before it, so one
+// thread per row ranks by counting, with no sort:
+//     rankD[f] = #{g < f : key[g] >= key[f]} + #{g > f : key[g] > key[f]},
+//     rankA[f] = #{g < f : key[g] <= key[f]} + #{g > f : key[g] < key[f]}.
+// Both ranks are bijections onto 0 .. F-1, so slot s of idx_out / val_out
+// [kt + kb][n] (kt top slots, then kb bottom slots) is written exactly once:
+// (f, phi[f]) goes to slot rankD[f] when rankD[f] < kt and to slot kt + rankA[f]
+// when rankA[f] < kb.  Nothing depends on an order of execution and no float is
+// computed, so results are bit-identical between calls.  Keys are finite (sums
+// of leaf values); a NaN key compares false both ways and its slot is undefined.
+//
+// kRankC candidates are held in registers per sweep over the keys, so a key is
+// read F / kRankC times.  The sweep has three parts, each with compile-time
+// comparisons: features before the candidates (>=, <=), the candidates against
+// each other (unrolled: the relation of two of them is their register index),
+// and features after them (>, <).  For F <= 64 the keys are staged in LDS as
+// [f][256] (a lane keeps its bank, every thread reads only its own column, so no
+// barrier); above that they are re-read from the planes, which a workgroup keeps
+// in cache (256 x F floats).
+namespace {
+
+constexpr int kRankC = 4;
+constexpr int kRankLdsF = 64;  // F * 1 KiB of keys per workgroup within the file's 64 KiB budget
+
+template <bool LDS, bool ABS>
+__global__ __launch_bounds__(256) void contrib_rank_kernel(const float* __restrict__ phi, int64_t ld, int64_t n,
+                                                           int F, int kt, int kb, int* __restrict__ idx_out,
+                                                           float* __restrict__ val_out) {
+  extern __shared__ float keys[];  // [F][256] when LDS
+  const int tid = threadIdx.x;
+  const int64_t r = (int64_t)blockIdx.x * 256 + tid;
+  if (r >= n) return;
+  const float* __restrict__ col = phi + r;
+  auto plane = [&](int g) -> float {
+    const float x = col[(int64_t)g * ld];
+    return ABS ? fabsf(x) : x;
+  };
+  auto key = [&](int g) -> float { return LDS ? keys[g * 256 + tid] : plane(g); };
+  if (LDS)
+    for (int g = 0; g < F; ++g) keys[g * 256 + tid] = plane(g);
+  for (int f0 = 0; f0 < F; f0 += kRankC) {
+    float kf[kRankC];
+    int rd[kRankC], ra[kRankC];
+#pragma unroll
+    for (int c = 0; c < kRankC; ++c) {
+      // candidates past F repeat the last feature; they are counted and never written
+      kf[c] = key(f0 + c < F ? f0 + c : F - 1);
+      rd[c] = 0;
+      ra[c] = 0;
+    }
+#pragma unroll 4
+    for (int g = 0; g < f0; ++g) {
+      const float kg = key(g);
+#pragma unroll
+      for (int c = 0; c < kRankC; ++c) {
+        rd[c] += kg >= kf[c] ? 1 : 0;
+        ra[c] += kg <= kf[c] ? 1 : 0;
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < kRankC; ++j) {
+      if (f0 + j < F) {
+#pragma unroll
+        for (int c = 0; c < kRankC; ++c) {
+          if (j < c) {
+            rd[c] += kf[j] >= kf[c] ? 1 : 0;
+            ra[c] += kf[j] <= kf[c] ? 1 : 0;
+          } else if (j > c) {
+            rd[c] += kf[j] > kf[c] ? 1 : 0;
+            ra[c] += kf[j] < kf[c] ? 1 : 0;
+          }
+        }
+      }
+    }
+#pragma unroll 4
+    for (int g = f0 + kRankC; g < F; ++g) {
+      const float kg = key(g);
+#pragma unroll
+      for (int c = 0; c < kRankC; ++c) {
+        rd[c] += kg > kf[c] ? 1 : 0;
+        ra[c] += kg < kf[c] ? 1 : 0;
+      }
+    }
+#pragma unroll
+    for (int c = 0; c < kRankC; ++c) {
+      const int f = f0 + c;
+      if (f < F) {
+        // the reported value keeps its sign (and the sign of a zero)
+        const float v = ABS ? col[(int64_t)f * ld] : kf[c];
+        if (rd[c] < kt) {
+          idx_out[(int64_t)rd[c] * n + r] = f;
+          val_out[(int64_t)rd[c] * n + r] = v;
+        }
+        if (ra[c] < kb) {
+          idx_out[(int64_t)(kt + ra[c]) * n + r] = f;
+          val_out[(int64_t)(kt + ra[c]) * n + r] = v;
+        }
+      }
+    }
+  }
+}
+
+}  // namespace
+
+// The kt first features of every row in descending and the kb first in
+// ascending order of the key (phi, or |phi| with compare_abs), ties to the
+// lower feature index: phi is [F][ld] with ld >= n, idx_out (feature indices)
+// and val_out (the signed phi) are [kt + kb][n], top slots first.
+H2OMX_API int h2omx_contrib_rank(const float* phi, int64_t ld, int64_t n, int F, int kt, int kb, int compare_abs,
+                                 int* idx_out, float* val_out, hipStream_t stream) {
+  if (n <= 0) return kOk;
+  if (F <= 0 || kt < 0 || kb < 0 || kt > F || kb > F || kt + kb == 0 || ld < n) return kBadArg;
+  const int64_t gx = (n + 255) / 256;
+  if (gx > 0x7FFFFFFF) return kBadArg;
+  const bool lds = F <= kRankLdsF;
+  const size_t shm = lds ? (size_t)F * 256 * sizeof(float) : 0;
+#define LAUNCH_RANK(L, A)                                                                                        \
+  hipLaunchKernelGGL((contrib_rank_kernel<L, A>), dim3((unsigned)gx), dim3(256), shm, stream, phi, ld, n, F, kt, \
+                     kb, idx_out, val_out)
+  if (lds) {
+    if (compare_abs) LAUNCH_RANK(true, true);
+    else LAUNCH_RANK(true, false);
+  } else {
+    if (compare_abs) LAUNCH_RANK(false, true);
+    else LAUNCH_RANK(false, false);
+  }
+#undef LAUNCH_RANK
+  return launch_status();
+}

@@ -10,6 +10,10 @@ table); on CPU frames the same path formula runs vectorised in NumPy.
 With ``background_frame=`` the same path table gives interventional
 (baseline) SHAP against every background row, averaged over the background
 or, with ``output_per_reference=True``, one row per (row, background row).
+``top_n=`` / ``bottom_n=`` / ``compare_abs=`` return, for any of these forms,
+each row's strongest features by name and value instead of every column; on
+the device contrib_rank_kernel ranks the contribution planes where the SHAP
+kernels left them.
 
 ``friedman_h(model, frame, variables)`` (H2O ``model.h``): Friedman and
 Popescu's H statistic of 2 or more numerical variables, from the partial
@@ -261,7 +265,105 @@ def _shap_background_device(X: torch.Tensor, Bm: torch.Tensor, lv, el, maxm, set
     return out
 
 
-def _contributions_background(model, ens, X, Bm, lv, el, maxm, sets, per_reference: bool) -> Frame:
+# ---------------------------------------------------------------------------
+# Ranked contributions (top_n / bottom_n / compare_abs)
+# ---------------------------------------------------------------------------
+def _rank_count(v, name: str) -> int:
+    if v is None:
+        return 0
+    if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.integer, np.floating)):
+        raise ValueError(f"{name} must be an integer, got {v!r}")
+    if not math.isfinite(v) or int(v) != v:
+        raise ValueError(f"{name} must be an integer, got {v!r}")
+    return int(v)
+
+
+def _rank_spec(top_n, bottom_n, F: int) -> tuple[int, int]:
+    """(kt, kb): how many features of the descending and of the ascending
+    order H2O's ``top_n`` / ``bottom_n`` ask for among F; (0, 0) is the
+    unsorted frame.  A negative count means all of them."""
+    t, b = _rank_count(top_n, "top_n"), _rank_count(bottom_n, "bottom_n")
+    if t == 0 and b == 0:
+        return 0, 0
+    if t != 0 and (t < 0 or b < 0):
+        return F, 0
+    if t == 0:
+        return (0, F) if b < 0 else (0, min(b, F))
+    if b == 0:
+        return min(t, F), 0
+    return (F, 0) if t + b >= F else (t, b)
+
+
+def _output_format(output_format) -> None:
+    # "Original" and "Compact" name the same frame here: no model one-hot expands a contribution column
+    if str(output_format).lower() not in ("original", "compact"):
+        raise ValueError(f"output_format must be 'Original' or 'Compact', got {output_format!r}")
+
+
+def _rank_numpy(phi: np.ndarray, kt: int, kb: int, compare_abs: bool):
+    """The oracle of :func:`_rank_device` on phi [F][n] float32: (idx int32,
+    val float32), both [kt + kb][n].  Descending sorts (-key, index) and
+    ascending (key, index), each a stable argsort, so ties go to the lower
+    index in both and the ascending order is not the descending one reversed."""
+    phi = np.asarray(phi, np.float32)
+    key = np.abs(phi) if compare_abs else phi
+    desc = np.argsort(-key, axis=0, kind="stable")[:kt]
+    asc = np.argsort(key, axis=0, kind="stable")[:kb]
+    idx = np.concatenate([desc, asc], 0)
+    return idx.astype(np.int32), np.take_along_axis(phi, idx, 0)
+
+
+def _rank_device(phi: torch.Tensor, kt: int, kb: int, compare_abs: bool):
+    """The HIP path (csrc/explain_kernels.hip contrib_rank_kernel) on a device
+    tensor phi [F][n] float32 whose rows are contiguous."""
+    from .ops import P, check, explain_lib, stream
+
+    F, n = (int(a) for a in phi.shape)
+    if phi.dtype != torch.float32 or (n > 1 and phi.stride(1) != 1) or (F > 1 and phi.stride(0) < n):
+        phi = phi.float().contiguous()
+    ld = max(int(phi.stride(0)), n) if F > 1 else n
+    idx = torch.empty((kt + kb, n), dtype=torch.int32, device=phi.device)
+    val = torch.empty((kt + kb, n), dtype=torch.float32, device=phi.device)
+    check(explain_lib().h2omx_contrib_rank(P(phi), ld, n, F, kt, kb, int(bool(compare_abs)), P(idx), P(val),
+                                           stream(phi.device)), "contrib_rank")
+    return idx, val
+
+
+def _rank(phi: torch.Tensor, kt: int, kb: int, compare_abs: bool):
+    if phi.is_cuda:
+        return _rank_device(phi, kt, kb, compare_abs)
+    idx, val = _rank_numpy(phi.float().numpy(), kt, kb, compare_abs)
+    return torch.from_numpy(idx), torch.from_numpy(val)
+
+
+def _ranked_frame(names, idx: torch.Tensor, val: torch.Tensor, lead_vecs, bias: Vec, *, kt: int) -> Frame:
+    """``lead_vecs``, then top_feature_i / top_value_i for the kt first slots
+    of idx / val and bottom_feature_i / bottom_value_i for the rest, then
+    ``bias``.  The feature columns are categorical over ``names``."""
+    dom = list(names)
+    vecs = list(lead_vecs)
+    for s in range(idx.shape[0]):
+        side, i = ("top", s + 1) if s < kt else ("bottom", s - kt + 1)
+        vecs.append(Vec(f"{side}_feature_{i}", idx[s], ENUM, dom))
+        vecs.append(Vec(f"{side}_value_{i}", val[s], "real"))
+    vecs.append(bias)
+    return Frame(vecs)
+
+
+def rank_contributions(frame: Frame, top_n, bottom_n, compare_abs: bool, nlead: int = 0) -> Frame:
+    """The ranked form of an unsorted contribution frame: ``nlead`` leading
+    index columns, the contribution columns, ``BiasTerm``.  Shared by the models
+    whose contributions are not [F][n] planes to begin with (GLM / GAM)."""
+    cols = frame.vecs[nlead:-1]
+    kt, kb = _rank_spec(top_n, bottom_n, len(cols))
+    if kt + kb == 0:
+        return frame
+    idx, val = _rank(torch.stack([v.data.float() for v in cols]), kt, kb, bool(compare_abs))
+    return _ranked_frame([v.name for v in cols], idx, val, frame.vecs[:nlead], frame.vecs[-1], kt=kt)
+
+
+def _contributions_background(model, ens, X, Bm, lv, el, maxm, sets, per_reference: bool, kt: int = 0, kb: int = 0,
+                              compare_abs: bool = False) -> Frame:
     F, n = X.shape
     nb = int(Bm.shape[1])
     if nb == 0:
@@ -269,6 +371,8 @@ def _contributions_background(model, ens, X, Bm, lv, el, maxm, sets, per_referen
     Bm = Bm.to(X.device)
     L = int(lv.shape[0])
     result = 4 * n * (nb * (F + 3) if per_reference else F + 1)
+    if per_reference:
+        result += 8 * (kt + kb) * n * nb
     if X.is_cuda:
         if maxm > 32:
             raise ValueError(f"a path of this model splits on {maxm} distinct features; the device kernel takes 32")
@@ -299,20 +403,32 @@ def _contributions_background(model, ens, X, Bm, lv, el, maxm, sets, per_referen
         bias = margin_b.to(dev).repeat(n)
     else:
         bias = torch.full((n,), float(margin_b.double().mean()), dtype=torch.float32, device=dev)
+    if kt + kb:
+        idx, val = _rank(out, kt, kb, compare_abs)
+        return _ranked_frame(model.x, idx, val, vecs, Vec("BiasTerm", bias, "real"), kt=kt)
     vecs += [Vec(c, out[j], "real") for j, c in enumerate(model.x)]
     vecs.append(Vec("BiasTerm", bias, "real"))
     return Frame(vecs)
 
 
 def predict_contributions(model, frame: Frame, *, background_frame: Frame | None = None,
-                          output_per_reference: bool = False) -> Frame:
+                          output_per_reference: bool = False, top_n=None, bottom_n=None, compare_abs: bool = False,
+                          output_format: str = "Original") -> Frame:
     """Path-dependent TreeSHAP, or with ``background_frame`` interventional
     (baseline) SHAP: every scored row x is explained against every background
     row b by the Shapley values of the game "coalition features from x, the
     rest from b".  The default averages over the background (one row per
     scored row, ``BiasTerm`` = mean background margin);
     ``output_per_reference`` returns one row per pair, x-major, led by
-    ``RowIdx`` and ``BackgroundRowIdx``, with ``BiasTerm`` = margin(b)."""
+    ``RowIdx`` and ``BackgroundRowIdx``, with ``BiasTerm`` = margin(b).
+
+    ``top_n`` / ``bottom_n`` give the ranked form of any of the three: per row
+    (per pair) the strongest features of the descending and of the ascending
+    order as ``top_feature_i`` / ``top_value_i`` and ``bottom_feature_i`` /
+    ``bottom_value_i`` (see :func:`_rank_spec`); ``compare_abs`` orders by
+    magnitude, the values keep their sign.  Ties go to the lower column index
+    in both orders."""
+    _output_format(output_format)
     ens = getattr(model, "ens", None)
     if ens is None or model.algo not in ("gbm", "drf", "xgboost", "generic"):
         raise NotImplementedError(f"predict_contributions is available for tree models, not {model.algo}")
@@ -323,6 +439,7 @@ def predict_contributions(model, frame: Frame, *, background_frame: Frame | None
     frame = model.adapt_frame(frame)
     X = model._matrix(frame) if hasattr(model, "_matrix") else frame.feature_matrix(model.x)
     F, n = X.shape
+    kt, kb = _rank_spec(top_n, bottom_n, F)
     nt = ens.ntrees
     scale = 1.0 / nt if (ens.average and nt > 0) else 1.0
     cb = getattr(ens, "catbits", None)
@@ -330,7 +447,8 @@ def predict_contributions(model, frame: Frame, *, background_frame: Frame | None
     if background_frame is not None:
         bg = model.adapt_frame(background_frame)
         Bm = model._matrix(bg) if hasattr(model, "_matrix") else bg.feature_matrix(model.x)
-        return _contributions_background(model, ens, X, Bm, lv, el, maxm, sets, bool(output_per_reference))
+        return _contributions_background(model, ens, X, Bm, lv, el, maxm, sets, bool(output_per_reference), kt, kb,
+                                         bool(compare_abs))
     bias = expected + (0.0 if ens.average else float(ens.init_f[0]))
     if X.is_cuda:
         from .ops import P, check, explain_lib, stream
@@ -347,6 +465,10 @@ def predict_contributions(model, frame: Frame, *, background_frame: Frame | None
                                             maxm, P(out), P(setd), stream(dev)), "tree_shap")
     else:
         out = torch.from_numpy(_shap_numpy(X.double().numpy(), lv, el, maxm, sets).astype(np.float32))
+    if kt + kb:
+        idx, val = _rank(out, kt, kb, bool(compare_abs))
+        bias_vec = Vec("BiasTerm", torch.full((n,), float(bias), dtype=torch.float32, device=out.device), "real")
+        return _ranked_frame(model.x, idx, val, [], bias_vec, kt=kt)
     vecs = [Vec(c, out[j], "real") for j, c in enumerate(model.x)]
     vecs.append(Vec("BiasTerm", torch.full((n,), float(bias), dtype=torch.float32, device=out.device), "real"))
     return Frame(vecs)

@@ -181,7 +181,19 @@ def _glm_contributions_background(model, Xs: torch.Tensor, Bs: torch.Tensor, per
 
 
 def glm_contributions(model, frame: Frame, *, background_frame: Frame | None = None,
-                      output_per_reference: bool = False) -> Frame:
+                      output_per_reference: bool = False, top_n=None, bottom_n=None, compare_abs: bool = False,
+                      output_format: str = "Original") -> Frame:
+    """Linear SHAP values per predictor (one-hot columns folded back) plus
+    ``BiasTerm``; ``top_n`` / ``bottom_n`` / ``compare_abs`` rank them per row
+    as :func:`h2omx.explain.predict_contributions` does."""
+    from .explain import _output_format, rank_contributions
+
+    _output_format(output_format)
+    out = _glm_contributions(model, frame, background_frame, output_per_reference)
+    return rank_contributions(out, top_n, bottom_n, compare_abs, nlead=2 if output_per_reference else 0)
+
+
+def _glm_contributions(model, frame: Frame, background_frame: Frame | None, output_per_reference: bool) -> Frame:
     if model.algo not in ("glm", "gam") or model.family == "multinomial" or model.family == "ordinal":
         raise NotImplementedError("linear contributions: single-output GLMs")
     if output_per_reference and background_frame is None:

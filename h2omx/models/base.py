@@ -156,13 +156,16 @@ class Model:
         return []
 
     def predict_contributions(self, frame: Frame, *, background_frame: Frame | None = None,
-                              output_per_reference: bool = False) -> Frame:
+                              output_per_reference: bool = False, top_n=None, bottom_n=None,
+                              compare_abs: bool = False, output_format: str = "Original") -> Frame:
         """SHAP contributions + BiasTerm (tree models; h2omx.explain).  With ``background_frame``:
-        interventional SHAP against its rows, averaged or (``output_per_reference``) pair by pair."""
+        interventional SHAP against its rows, averaged or (``output_per_reference``) pair by pair.
+        ``top_n`` / ``bottom_n`` / ``compare_abs``: per row the strongest features by name and value."""
         from ..explain import predict_contributions
 
         return predict_contributions(self, frame, background_frame=background_frame,
-                                     output_per_reference=output_per_reference)
+                                     output_per_reference=output_per_reference, top_n=top_n, bottom_n=bottom_n,
+                                     compare_abs=compare_abs, output_format=output_format)
 
     def h(self, frame: Frame, variables) -> float:
         """Friedman and Popescu's H statistic of 2 or more numerical predictors (tree models; h2omx.explain)."""

@@ -218,12 +218,14 @@ class GLMModel(Model):
         return mu[None, :].float()
 
     def predict_contributions(self, frame: Frame, *, background_frame: Frame | None = None,
-                              output_per_reference: bool = False) -> Frame:
+                              output_per_reference: bool = False, top_n=None, bottom_n=None,
+                              compare_abs: bool = False, output_format: str = "Original") -> Frame:
         """Exact linear SHAP values in link space (explain_more.glm_contributions)."""
         from ..explain_more import glm_contributions
 
         return glm_contributions(self, frame, background_frame=background_frame,
-                                 output_per_reference=output_per_reference)
+                                 output_per_reference=output_per_reference, top_n=top_n, bottom_n=bottom_n,
+                                 compare_abs=compare_abs, output_format=output_format)
 
     def varimp(self):
         b = np.abs(self.beta_std[:, :-1]).sum(0)

@@ -132,6 +132,8 @@ EXPLAIN_SIGS = {
     "h2omx_friedman_h_pd": "PLLIIIIIIIIPPIIPPS",
     # X, ld, n, F, nodes, roots, ntrees, K, catbits, fs, grid, ub, G, gn, ff, fixed, ny, out, walks
     "h2omx_pd_sweep": "PLLIPPIIPIPPIIIPIPPS",
+    # phi, ld, n, F, kt, kb, compare_abs, idx_out, val_out
+    "h2omx_contrib_rank": "PLLIIIIPPS",
 }
 
 P2P_SIGS = {

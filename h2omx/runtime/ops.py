@@ -181,23 +181,31 @@ def op_train(cl, algo, params, x=None, y=None, training_frame=None, validation_f
 
 
 def op_predict(cl, model, frame, dest, kind="predict", leaf_type="Path", background_frame=None,
-               output_per_reference=False):
+               output_per_reference=False, top_n=None, bottom_n=None, compare_abs=False, output_format=None):
     m = _model(model)
     fr = _frame(frame)
     if kind != "contributions" and (background_frame or output_per_reference):
         raise ValueError("background_frame and output_per_reference belong to predict_contributions")
+    if kind != "contributions" and (top_n or bottom_n or compare_abs or output_format):
+        raise ValueError("top_n, bottom_n, compare_abs and output_format belong to predict_contributions")
+    # ranking is per row and rows are sharded: every rank ranks its own rows
+    rank_kw = {}
+    if top_n or bottom_n or compare_abs or output_format:
+        rank_kw = dict(top_n=top_n, bottom_n=bottom_n, compare_abs=bool(compare_abs),
+                       output_format=output_format or "Original")
     if kind == "contributions" and (background_frame or output_per_reference):
         if not background_frame:
             raise ValueError("output_per_reference=True needs a background_frame")
         # every rank explains its shard of the scored rows against all background rows
         comm = cl.comm if cl.world_size > 1 else None
         bg = gather_frame(_frame(background_frame), comm)
-        pf = m.predict_contributions(fr, background_frame=bg, output_per_reference=bool(output_per_reference))
+        pf = m.predict_contributions(fr, background_frame=bg, output_per_reference=bool(output_per_reference),
+                                     **rank_kw)
         if output_per_reference and comm is not None:
             counts = comm.all_gather_cat(torch.tensor([fr.nrows], dtype=torch.int64, device=fr.device))
             pf.vec("RowIdx").data += float(counts[:cl.rank].sum())     # RowIdx counts rows of the whole frame
     elif kind == "contributions":
-        pf = m.predict_contributions(fr)
+        pf = m.predict_contributions(fr, **rank_kw)
     elif kind == "leaf_nodes":
         pf = m.predict_leaf_node_assignment(fr, leaf_type)
     elif kind == "staged_proba":
