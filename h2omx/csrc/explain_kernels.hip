@@ -15,6 +15,16 @@
 // element loads are wave-uniform (scalar / broadcast) and the per-feature
 // accumulators are written coalesced: in LDS ([F][256] per workgroup) when
 // they fit, else straight to the feature-major output.
+//
+// Precision.  Followed elements (o_i = 1) are taken out of P by synthetic
+// division from the top coefficient, which carries the rounding error of the
+// middle coefficients, eps C(m, m/2) when the z_j are near 1, down to the
+// constant term.  In fp32 that stays below 1e-5 per unit leaf value up to
+// m = 16 and reaches 1e-1 at m = 32 (measured against tests/shapref.py), so
+// the MAXM = 32 instantiation keeps P and the division in fp64 (2^-53 C(32, 16)
+// = 7e-8); the two narrower ones are fp32 throughout.
+#include <type_traits>
+
 #include "common.h"
 
 namespace {
@@ -25,6 +35,9 @@ __global__ __launch_bounds__(256) void tree_shap_kernel(const float* __restrict_
                                                         const float4* __restrict__ elems,
                                                         const float* __restrict__ wtab, float* __restrict__ out,
                                                         const uint32_t* __restrict__ sets) {
+  // fp32 for MAXM <= 16; the 32-wide instantiation carries P and the division in fp64
+  // (see the header).  z and o are kept as the float32 they were read as, which is exact.
+  using T = typename std::conditional<(MAXM > 16), double, float>::type;
   extern __shared__ float acc[];
   __shared__ float w_s[(MAXM + 1) * (MAXM + 1)];
   const int tid = threadIdx.x;
@@ -41,7 +54,7 @@ __global__ __launch_bounds__(256) void tree_shap_kernel(const float* __restrict_
     const float v = __int_as_float(hd.z);
     float z[MAXM], o[MAXM];
     int fe[MAXM];
-    float P[MAXM + 1];
+    T P[MAXM + 1];
     P[0] = 1.0f;
 #pragma unroll
     for (int k = 1; k <= MAXM; ++k) P[k] = 0.0f;
@@ -64,37 +77,38 @@ __global__ __launch_bounds__(256) void tree_shap_kernel(const float* __restrict_
         } else {
           oj = (x > e.z && x <= e.w) ? 1.0f : 0.0f;
         }
+        const T zj = e.y, ojt = oj;
         z[j] = e.y; o[j] = oj; fe[j] = f;
 #pragma unroll
         for (int k = MAXM; k >= 1; --k)
-          if (k <= j + 1) P[k] = e.y * P[k] + oj * P[k - 1];
-        P[0] *= e.y;
+          if (k <= j + 1) P[k] = zj * P[k] + ojt * P[k - 1];
+        P[0] *= zj;
       }
     }
     const float* wm = w_s + m * (MAXM + 1);
 #pragma unroll
     for (int i = 0; i < MAXM; ++i) {
       if (i < m) {
-        const float zi = z[i], oi = o[i];
-        float s = 0.0f;
+        const T zi = z[i], oi = o[i];
+        T s = 0.0f;
         if (oi != 0.0f) {
           // P / (z_i + t) by synthetic division from the top coefficient
-          float carry = 0.0f;
+          T carry = 0.0f;
 #pragma unroll
           for (int k = MAXM; k >= 1; --k) {
             if (k <= m) {
-              const float q = P[k] - zi * carry;
+              const T q = P[k] - zi * carry;
               s += q * wm[k - 1];
               carry = q;
             }
           }
         } else if (zi > 0.0f) {
-          const float inv = 1.0f / zi;
+          const T inv = 1.0f / zi;
 #pragma unroll
           for (int k = 0; k < MAXM; ++k)
             if (k < m) s += P[k] * inv * wm[k];
         }
-        const float phi = v * (oi - zi) * s;
+        const float phi = (float)(v * (oi - zi) * s);
         if (LDS) acc[fe[i] * 256 + tid] += phi;
         else if (live) out[(int64_t)fe[i] * n + r] += phi;
       }

@@ -177,6 +177,30 @@ def _shap_numpy(X: np.ndarray, lv, el, maxm, sets=None) -> np.ndarray:
     return out
 
 
+def _shap_device(X: torch.Tensor, lv, el, maxm, sets) -> torch.Tensor:
+    """The HIP path (csrc/explain_kernels.hip tree_shap_kernel): [F][n] float32
+    contributions of the device rows X [F][n] over the path table."""
+    from .ops import P, check, explain_lib, stream
+
+    F, n = X.shape
+    dev = X.device
+    Xc = X.float().contiguous()
+    M = _bucket(maxm)
+    wt = torch.from_numpy(shapley_weights(M).astype(np.float32)).to(dev)
+    lvd = torch.from_numpy(lv).to(dev)
+    eld = torch.from_numpy(el if el.size else np.zeros((1, 4), np.float32)).to(dev)
+    out = torch.zeros((F, n), dtype=torch.float32, device=dev)
+    setd = torch.from_numpy(sets.view(np.int32).copy()).to(dev)
+    rc = explain_lib().h2omx_tree_shap(P(Xc), Xc.stride(0), n, F, P(lvd), int(lv.shape[0]), P(eld), P(wt),
+                                       maxm, P(out), P(setd), stream(dev))
+    if rc != 0 and maxm > 32:
+        raise RuntimeError(f"h2omx native call tree_shap failed with status {rc}: a path of this model splits on "
+                           f"{maxm} distinct features; paths with more than 32 distinct features are unsupported "
+                           "on the device")
+    check(rc, "tree_shap")
+    return out
+
+
 def baseline_weights(M: int = 32) -> np.ndarray:
     """T[a][c] = (a-1)! c! / (a+c)! for 1 <= a <= M, 0 <= c <= M (row 0 is
     zero).  For a leaf whose elements split into a followed only by the scored
@@ -451,18 +475,7 @@ def predict_contributions(model, frame: Frame, *, background_frame: Frame | None
                                          bool(compare_abs))
     bias = expected + (0.0 if ens.average else float(ens.init_f[0]))
     if X.is_cuda:
-        from .ops import P, check, explain_lib, stream
-
-        dev = X.device
-        Xc = X.float().contiguous()
-        M = _bucket(maxm)
-        wt = torch.from_numpy(shapley_weights(M).astype(np.float32)).to(dev)
-        lvd = torch.from_numpy(lv).to(dev)
-        eld = torch.from_numpy(el if el.size else np.zeros((1, 4), np.float32)).to(dev)
-        out = torch.zeros((F, n), dtype=torch.float32, device=dev)
-        setd = torch.from_numpy(sets.view(np.int32).copy()).to(dev)
-        check(explain_lib().h2omx_tree_shap(P(Xc), Xc.stride(0), n, F, P(lvd), int(lv.shape[0]), P(eld), P(wt),
-                                            maxm, P(out), P(setd), stream(dev)), "tree_shap")
+        out = _shap_device(X, lv, el, maxm, sets)
     else:
         out = torch.from_numpy(_shap_numpy(X.double().numpy(), lv, el, maxm, sets).astype(np.float32))
     if kt + kb:
