@@ -43,7 +43,7 @@ def glm_grad_pass(X: torch.Tensor, y: torch.Tensor, wprior, offset, beta: np.nda
             dmu = np.maximum(mu * (1 - mu), 1e-10)
         dmu = np.maximum(dmu, 1e-10) if link in ("log", "tweedie") and link_power == 0 else dmu
         R = (w * (mu - yn) * dmu / glm_variance(family, mu, var_power))[None, :]
-        dev = float((w * glm_deviance(family, yn, mu, var_power)).sum())
+        dev = float((w * glm_deviance(family, yn, mu, var_power, e0 if link == "logit" else None)).sum())
     g = np.concatenate([R @ Xn.T, R.sum(1, keepdims=True)], axis=1)
     return g, dev
 
@@ -82,13 +82,21 @@ def glm_variance(family, mu, var_power=1.5):
     return np.ones_like(mu)
 
 
-def glm_deviance(family, y, mu, var_power=1.5):
+def glm_deviance(family, y, mu, var_power=1.5, eta=None):
+    """Unit deviance.  ``eta``: the linear predictor of a logit link; the
+    binomial family then takes log mu and log(1 - mu) from it (stable for
+    saturated rows), floored at log(1e-15) like the clamp of mu otherwise."""
     if family == "negativebinomial":
         th, m = var_power, np.maximum(mu, 1e-15)
         with np.errstate(divide="ignore", invalid="ignore"):
             a = np.where(y > 0, y * np.log(np.where(y > 0, y, 1) / m), 0.0)
         return 2 * (a - (y + 1 / th) * np.log((1 + th * y) / (1 + th * m)))
     if family in ("binomial", "quasibinomial", "fractionalbinomial"):
+        if eta is not None:
+            l1p = np.log1p(np.exp(-np.abs(eta)))
+            lm = np.maximum(np.minimum(eta, 0) - l1p, np.log(1e-15))
+            l1m = np.maximum(-np.maximum(eta, 0) - l1p, np.log(1e-15))
+            return -2 * (y * lm + (1 - y) * l1m)
         m = np.clip(mu, 1e-15, 1 - 1e-15)
         return -2 * (y * np.log(m) + (1 - y) * np.log(1 - m))
     if family == "poisson":
@@ -134,7 +142,7 @@ def _irls_pass_ref(X, y, wprior, offset, beta, family, link, cls, var_power, lin
             dmu = np.maximum(mu, 1e-10)
         w = wp * dmu * dmu / glm_variance(family, mu, var_power)
         z = eta - off + (yv - mu) / dmu
-        dev = float((wp * glm_deviance(family, yv, mu, var_power)).sum())
+        dev = float((wp * glm_deviance(family, yv, mu, var_power, eta if link == "logit" else None)).sum())
     A = np.vstack([Xn, np.ones((1, n)), z[None, :]])
     sw = np.sqrt(np.maximum(w, 0))
     As = A * sw[None, :]
