@@ -931,7 +931,40 @@ __device__ void level_fin_records(const FeatBest* __restrict__ fbest, const int*
 }
 
 constexpr int CMP_STAGE_BYTES = 2048;   // per wave
-constexpr int HB_PF = 1;     // feature code loads kept in flight per lane
+// Feature loop of the histogram kernel: one trip handles HB_PF features and
+// issues the next trip's code loads, 16 atomics per feature before the loop's
+// back edge drains them (s_waitcnt vmcnt(0)) - at most ~1.5 loads in flight
+// per lane whatever HB_PF is, one exposed memory round trip per trip.  The
+// batched loop below (FG_MAX) replaces it where the engine selects it.
+constexpr int HB_PF = 1;
+// Batched loop (mode bit 7, engine.py HIST_BATCH): the level-0 kernels (PKM
+// 1 / 3 / 6, one slot, 16-row units) issue a row unit's packed-row loads and the
+// code loads of ALL the group's planes together, into registers, and consume
+// them in issue order in straight-line code (descending s_waitcnt vmcnt(k), no
+// drain between a unit's features).  Groups wider than FG_MAX planes keep the
+// feature loop, and so do the deeper levels: the plain last level measured
+// slower with this loop (profiles/r14/hist_stream_ab.txt).
+// The kernel always issues FG_MAX code loads: a group of nf < FG_MAX planes
+// re-reads its last plane FG_MAX - nf times (the same 16 bytes per lane, L1 /
+// L2 hits, never consumed), which is what keeps every wait a counted one.  Their
+// cost alone was not measured; the 1.375M-row shard, whose level 0 runs such
+// groups, is faster with the loop than without (16.6 vs 19.0 us).
+constexpr int FG_MAX = 8;
+
+// 16-bit packed row (int16 G_q << 16 | uint16 S_q) -> the 64-bit histogram addend
+__device__ __forceinline__ unsigned long long pk_widen(uint32_t pw) {
+  return ((unsigned long long)(uint32_t)(int)(short)(pw >> 16) << 32) | (unsigned long long)(pw & 0xFFFFu);
+}
+
+// dithered fixed-point row (g, s) -> the 64-bit histogram addend
+__device__ __forceinline__ unsigned long long pk_quantise(float gv, float sv, float sg, float ss, int64_t row,
+                                                          uint32_t salt) {
+  const uint32_t hsh = row_hash(row, salt);
+  const float d1 = (hsh & 0xFFFF) * (1.0f / 65536.0f), d2 = (hsh >> 16) * (1.0f / 65536.0f);
+  const int gq = (int)floorf(fmaf(gv, sg, d1));
+  const uint32_t sq = (uint32_t)floorf(fmaf(sv, ss, d2));
+  return ((unsigned long long)(uint32_t)gq << 32) | (unsigned long long)sq;
+}
 
 // COP > 1 (level 0, PKM 1 / 3): every (slot, feature, bin) entry is COP
 // interleaved u64 copies, [bin][copy], lane l adding into copy l % COP: the
@@ -947,7 +980,7 @@ constexpr int HB_PF = 1;     // feature code loads kept in flight per lane
 // nvb = NBT - 1: one full-width slice).  reduce_split marginalises the joint
 // rows back into per-feature rows.  The fused routing and the level prologue
 // read the split features' own planes of `codes` either way.
-template <int NBT, int ROWS, int PKM, bool ROUTE, bool CMP, int COP = 1, bool NID16 = false>
+template <int NBT, int ROWS, int PKM, bool ROUTE, bool CMP, int COP = 1, bool NID16 = false, bool BATCH = false>
 __global__ __launch_bounds__(1024) void hist_build_kernel(
     const uint8_t* __restrict__ codes, int64_t npad, const float* __restrict__ g, const float* __restrict__ s2,
     const int* __restrict__ nid, const NodeLink* __restrict__ link, const int* __restrict__ ctl,
@@ -1013,6 +1046,26 @@ __global__ __launch_bounds__(1024) void hist_build_kernel(
   const int64_t rb = (int64_t)qscale[7];  // global row offset of this rank (dither)
   const int64_t n_rows = (int64_t)qscale[8];  // this rank's live rows (implicit-root levels)
   __syncthreads();
+
+  // batched loop: the planes' code bases and slice shapes, wave-uniform, once
+  // per workgroup (entries past nf repeat the last plane: their loads are
+  // issued - so every wait is a counted one - and never consumed)
+  static_assert(!BATCH || (!ROUTE && !CMP && (PKM == 1 || PKM == 3 || PKM == 6) && ROWS == 16),
+                "batched loop: level 0 (one slot: the launcher checks)");
+  constexpr int NQ = BATCH ? FG_MAX : 1;
+  const uint8_t* pbase[NQ];
+  int rep_q[NQ], width_q[NQ];
+  float rcp_q[NQ];
+  if constexpr (BATCH) {
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) {
+      const int fi = min(q, nf - 1);
+      pbase[q] = plane_codes(fi);
+      rep_q[q] = __builtin_amdgcn_readfirstlane(rep_s[fi]);
+      width_q[q] = __builtin_amdgcn_readfirstlane(width_s[fi]);
+      rcp_q[q] = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(rcp_s[fi])));
+    }
+  }
 
   const int64_t units = npad / ROWS;
   const int64_t u0 = units * chunk / wgpg, u1 = units * (chunk + 1) / wgpg;
@@ -1156,6 +1209,106 @@ __global__ __launch_bounds__(1024) void hist_build_kernel(
     } else {
       if (!any) continue;
     }
+    if constexpr (BATCH) {
+      uint32_t live = 0;   // rows in the histogram
+#pragma unroll
+      for (int r = 0; r < ROWS; ++r) live |= (s[r] >= 0 ? 1u : 0u) << r;
+      // issue: the unit's packed rows (PKM 6) or (g, s) rows, then every plane's codes
+      unsigned long long pk[ROWS];
+      uint4 raw4[PKM == 6 ? ROWS / 4 : 1];
+      float4 rawg[PKM == 6 ? 1 : ROWS / 4], raws[PKM == 6 ? 1 : ROWS / 4];
+      if constexpr (PKM == 6) {
+#pragma unroll
+        for (int q = 0; q < ROWS / 4; ++q)
+          raw4[q] = *reinterpret_cast<const uint4*>(reinterpret_cast<const uint32_t*>(pk_buf) + r0 + 4 * q);
+      } else {
+#pragma unroll
+        for (int q = 0; q < ROWS / 4; ++q) {
+          rawg[q] = *reinterpret_cast<const float4*>(g + r0 + 4 * q);
+          raws[q] = make_float4(1.f, 1.f, 1.f, 1.f);
+          if (s2) raws[q] = *reinterpret_cast<const float4*>(s2 + r0 + 4 * q);
+        }
+      }
+      uint4 cq[NQ];
+#pragma unroll
+      for (int q = 0; q < NQ; ++q) cq[q] = *reinterpret_cast<const uint4*>(pbase[q] + r0);
+      // every load is issued before the first one is waited for (the scheduler
+      // otherwise holds code loads back behind the packed rows' wait)
+      __builtin_amdgcn_sched_barrier(0);
+      // consume, in issue order
+      if constexpr (PKM == 6) {
+#pragma unroll
+        for (int q = 0; q < ROWS / 4; ++q) {
+          const uint32_t pw[4] = {raw4[q].x, raw4[q].y, raw4[q].z, raw4[q].w};
+#pragma unroll
+          for (int k = 0; k < 4; ++k) pk[4 * q + k] = pk_widen(pw[k]);
+        }
+      } else {
+#pragma unroll
+        for (int q = 0; q < ROWS / 4; ++q) {
+          const float gv[4] = {rawg[q].x, rawg[q].y, rawg[q].z, rawg[q].w};
+          const float sv[4] = {raws[q].x, raws[q].y, raws[q].z, raws[q].w};
+#pragma unroll
+          for (int k = 0; k < 4; ++k) pk[4 * q + k] = pk_quantise(gv[k], sv[k], sg, ss, rb + r0 + 4 * q + k, salt);
+        }
+        if (group == 0) {   // the packed rows the deeper levels read
+          if constexpr (PKM == 1) {
+#pragma unroll
+            for (int q = 0; q < ROWS / 2; ++q)
+              *reinterpret_cast<ulonglong2*>(pk_buf + r0 + 2 * q) = make_ulonglong2(pk[2 * q], pk[2 * q + 1]);
+          } else {
+            uint32_t* pk32 = reinterpret_cast<uint32_t*>(pk_buf);
+#pragma unroll
+            for (int q = 0; q < ROWS / 4; ++q) {
+              uint32_t pw[4];
+#pragma unroll
+              for (int k = 0; k < 4; ++k) {
+                const unsigned long long v = pk[4 * q + k];
+                pw[k] = ((uint32_t)(v >> 32) << 16) | ((uint32_t)v & 0xFFFFu);
+              }
+              *reinterpret_cast<uint4*>(pk32 + r0 + 4 * q) = make_uint4(pw[0], pw[1], pw[2], pw[3]);
+            }
+          }
+        }
+      }
+      // one slot: a row outside the histogram adds 0 at its own code's address -
+      // no exec mask per atomic (a code masked to NBT - 1 stays inside the
+      // plane's slice whatever a padding row holds).  (Bit mask and sign-extended
+      // bit extract: 16 lane masks held across the loads would spill SGPRs)
+#pragma unroll
+      for (int r = 0; r < ROWS; ++r) pk[r] &= (unsigned long long)(long long)((int)(live << (31 - r)) >> 31);
+#pragma unroll
+      for (int q = 0; q < NQ; ++q) {
+        if (q == 0 || q < nf) {   // (nf >= 1: plane 0's block is unconditional, its load stays with the others)
+          const uint32_t cw[4] = {cq[q].x, cq[q].y, cq[q].z, cq[q].w};
+          if (COP == 1 && rep_q[q] > 1) {
+            // replicated low-cardinality slice, as in the feature loop (masked:
+            // a padding row's code may lie outside the slice)
+            const int width = width_q[q];
+            const int copy = lane - rep_q[q] * (int)(((float)lane + 0.5f) * rcp_q[q]);
+            unsigned long long* hb = lds64 + q * NBT + copy * width;
+#pragma unroll
+            for (int r = 0; r < ROWS; ++r) {
+              if (pk[r] != 0ull) {
+                int bin = (cw[r >> 2] >> (8 * (r & 3))) & 0xff;
+                if (bin == NBT - 1) bin = width - 1;
+                atomicAdd(hb + bin, pk[r]);
+              }
+            }
+          } else {
+            unsigned long long* hb = lds64 + q * NBT * COP + (lane & (COP - 1));
+#pragma unroll
+            for (int r = 0; r < ROWS; ++r) atomicAdd(hb + ((cw[r >> 2] >> (8 * (r & 3))) & (NBT - 1)) * COP, pk[r]);
+          }
+        }
+      }
+      // a use of every plane's codes outside the guarded blocks: a load whose
+      // only use sits in the block behind `q < nf` is sunk into that block and
+      // drained there (vmcnt(0)); here every load has long landed
+#pragma unroll
+      for (int q = 1; q < NQ; ++q) __asm__ volatile("" ::"v"(cq[q].x), "v"(cq[q].y), "v"(cq[q].z), "v"(cq[q].w));
+      continue;
+    }
     // codes of the next HB_PF features are in flight while this feature's
     // atomics issue (one load per wave in flight starved HBM: ~3 TB/s); the
     // first ones are issued before the per-row inputs below, so their latency
@@ -1192,9 +1345,7 @@ __global__ __launch_bounds__(1024) void hist_build_kernel(
         const uint4 p4 = *reinterpret_cast<const uint4*>(pk32 + r0 + 4 * q);
         const uint32_t pw[4] = {p4.x, p4.y, p4.z, p4.w};
 #pragma unroll
-        for (int k = 0; k < 4; ++k)
-          pk[4 * q + k] = ((unsigned long long)(uint32_t)(int)(short)(pw[k] >> 16) << 32) |
-                          (unsigned long long)(pw[k] & 0xFFFFu);
+        for (int k = 0; k < 4; ++k) pk[4 * q + k] = pk_widen(pw[k]);
       }
     } else if constexpr (PKM == 5) {
 #pragma unroll
@@ -1245,13 +1396,7 @@ __global__ __launch_bounds__(1024) void hist_build_kernel(
       const float gv[4] = {g4.x, g4.y, g4.z, g4.w};
       const float sv[4] = {s4.x, s4.y, s4.z, s4.w};
 #pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        const uint32_t hsh = row_hash(rb + r0 + 4 * q + k, salt);
-        const float d1 = (hsh & 0xFFFF) * (1.0f / 65536.0f), d2 = (hsh >> 16) * (1.0f / 65536.0f);
-        const int gq = (int)floorf(fmaf(gv[k], sg, d1));
-        const uint32_t sq = (uint32_t)floorf(fmaf(sv[k], ss, d2));
-        pk[4 * q + k] = ((unsigned long long)(uint32_t)gq << 32) | (unsigned long long)sq;
-      }
+      for (int k = 0; k < 4; ++k) pk[4 * q + k] = pk_quantise(gv[k], sv[k], sg, ss, rb + r0 + 4 * q + k, salt);
     }
     if (PKM == 1 && group == 0) {
 #pragma unroll
@@ -3271,7 +3416,12 @@ static int hist_build_launch(const uint8_t* codes, int64_t npad, const float* g,
   const int cop = (pkm & 16) ? 8 : ((pkm & 32) ? 4 : 1);
   // pkm bit 6: int16 node-id streams (routed levels only)
   const bool nid16 = (pkm & 64) != 0;
+  // pkm bit 7: batched loop (FG_MAX) where the kernel has one: level 0 (pkm 1 / 3 / 6, one slot, 16-row units),
+  // groups of <= FG_MAX planes; anything else drops the bit and keeps the feature loop
+  bool batch = (pkm & 128) != 0;
   pkm &= 7;
+  if (route || cmp || (pkm != 1 && pkm != 3 && pkm != 6) || fg > FG_MAX || rows_per_lane != 16 || slot_cnt != 1)
+    batch = false;
   if (nid16 && (!route || cmp || rows_per_lane != 16)) return kBadArg;
   if (cop > 1 && ((pkm != 1 && pkm != 3 && pkm != 6) || route || cmp)) return kBadArg;
   // pkm 6: level 0 reading the packed rows boost_update wrote (implicit root)
@@ -3308,6 +3458,23 @@ static int hist_build_launch(const uint8_t* codes, int64_t npad, const float* g,
   hipLaunchKernelGGL((hist_build_kernel<NB, 16, M, true, false, 1, true>), dim3(grid), dim3(threads), lds, stream, \
                      codes, npad, g, s2, nid, lk, ctl, nvb, qscale, (uint32_t)salt, F, fg, n_groups, wgpg, slot_lo,    \
                      slot_cnt, slot16, pk_buf, partials, pp, ctl_prev, nid_out, writer, gfz, lpz, joint, plane_src)
+#define LAUNCH_HBB(NB, M, CP)                                                                                    \
+  hipLaunchKernelGGL((hist_build_kernel<NB, 16, M, false, false, CP, false, true>), dim3(grid), dim3(threads), lds, \
+                     stream, codes, npad, g, s2, nid, lk, ctl, nvb, qscale, (uint32_t)salt, F, fg, n_groups, wgpg,    \
+                     slot_lo, slot_cnt, slot16, pk_buf, partials, pp, ctl_prev, nid_out, writer, gfz, lpz, joint,     \
+                     plane_src)
+#define LAUNCH_HBATCH(NB)                                      \
+  do {                                                        \
+    if (pkm == 1 && cop == 8) LAUNCH_HBB(NB, 1, 8);            \
+    else if (pkm == 1 && cop == 4) LAUNCH_HBB(NB, 1, 4);       \
+    else if (pkm == 1) LAUNCH_HBB(NB, 1, 1);                   \
+    else if (pkm == 3 && cop == 8) LAUNCH_HBB(NB, 3, 8);       \
+    else if (pkm == 3 && cop == 4) LAUNCH_HBB(NB, 3, 4);       \
+    else if (pkm == 3) LAUNCH_HBB(NB, 3, 1);                   \
+    else if (cop == 8) LAUNCH_HBB(NB, 6, 8);                   \
+    else if (cop == 4) LAUNCH_HBB(NB, 6, 4);                   \
+    else LAUNCH_HBB(NB, 6, 1);                                 \
+  } while (0)
 #define LAUNCH_HB(NB, R)                                            \
   do {                                                             \
     if (pkm == 0) LAUNCH_HBK(NB, R, 0, false, false);               \
@@ -3333,7 +3500,15 @@ static int hist_build_launch(const uint8_t* codes, int64_t npad, const float* g,
     else if (route) LAUNCH_HBK(NB, 16, 4, true, true);               \
     else LAUNCH_HBK(NB, 16, 4, false, true);                         \
   } while (0)
-  if (cmp) {
+  if (batch) {
+    switch (nbt) {
+      case 32: LAUNCH_HBATCH(32); break;
+      case 64: LAUNCH_HBATCH(64); break;
+      case 128: LAUNCH_HBATCH(128); break;
+      case 256: LAUNCH_HBATCH(256); break;
+      default: return kBadArg;
+    }
+  } else if (cmp) {
     switch (nbt) {
       case 32: LAUNCH_HBCMP(32); break;
       case 64: LAUNCH_HBCMP(64); break;
@@ -3369,6 +3544,8 @@ static int hist_build_launch(const uint8_t* codes, int64_t npad, const float* g,
     return kBadArg;
   }
 #undef LAUNCH_HB
+#undef LAUNCH_HBATCH
+#undef LAUNCH_HBB
 #undef LAUNCH_HBK16
 #undef LAUNCH_HBCMP
 #undef LAUNCH_HBK

@@ -150,6 +150,17 @@ class HipTreeBuilder:
     # and the segmented engine keep one plane per feature
     BUNDLE = True
     PK32 = True
+    # level 0 runs hist_build's batched loop (mode bit 7): a row unit's packed
+    # rows and the codes of all the group's planes are loaded together and
+    # consumed in issue order, and every row is added unmasked.  Same int64 sums.
+    # HIST_FG_MAX is the widest group that loop takes - FG_MAX in
+    # csrc/tree_kernels.hip; nothing ties the two: a group wider than the kernel's
+    # FG_MAX drops the bit in the launcher and runs the feature loop - and the
+    # plans of level 0 are capped at it.  With L0_COPIES = 1 the cap splits one
+    # group of up to 64 planes into groups of 8, each re-reading the packed rows:
+    # that configuration (not a default) was not measured
+    HIST_BATCH = True
+    HIST_FG_MAX = 8
     FUSE_GRAD = False
     CHAIN_BEGIN = True
     # partition workgroups spread their leaf-sum folds over this many slices
@@ -377,10 +388,10 @@ class HipTreeBuilder:
     # feature groups of DEEP_LDS_BUDGET); 1 = plain slices
     L0_COPIES = 8
 
-    def plan_l0(self):
-        key = ("l0", self.L0_COPIES)
+    def plan_l0(self, fg_cap: int | None = None):
+        key = ("l0", self.L0_COPIES, fg_cap)
         if key not in self.plans:
-            self.plans[key] = self._plan(1, self.DEEP_LDS_BUDGET, self.THREADS, mult=self.L0_COPIES)
+            self.plans[key] = self._plan(1, self.DEEP_LDS_BUDGET, self.THREADS, mult=self.L0_COPIES, fg_cap=fg_cap)
         return self.plans[key]
 
     # grids that overflow one round of resident workgroups are widened to fill
@@ -412,7 +423,8 @@ class HipTreeBuilder:
     SMALL_SHARD = True
     FILL_ROUNDS = True
 
-    def _plan(self, max_slots: int, budget: int, threads: int, units: int | None = None, mult: int = 1):
+    def _plan(self, max_slots: int, budget: int, threads: int, units: int | None = None, mult: int = 1,
+              fg_cap: int | None = None):
         per_slot_feat = self.nbt * 8 * mult
         # the kernel's "features" are histogram planes (a builder without a plane
         # count - before __init__ set it, or none at all - plans one per feature)
@@ -430,6 +442,9 @@ class HipTreeBuilder:
         if passes == 1 and self.MIN_GROUPS > n_groups and mult == 1:
             fg = math.ceil(F / min(F, self.MIN_GROUPS))
             n_groups = math.ceil(F / fg)
+        if fg_cap is not None and fg > fg_cap:   # the batched loop's group width (HIST_BATCH)
+            n_groups = math.ceil(F / fg_cap)
+            fg = math.ceil(F / n_groups)
         if units is None:
             units = self.bm.npad // self.ROWS_PER_LANE
 
@@ -460,24 +475,25 @@ class HipTreeBuilder:
             wgpg = self._fill_rounds(wgpg, n_groups, slot_cnt * fg * per_slot_feat, threads, units)
         return dict(slot_cnt=slot_cnt, fg=fg, n_groups=n_groups, passes=passes, wgpg=wgpg, threads=threads)
 
-    def plan_level(self, max_slots: int):
+    def plan_level(self, max_slots: int, fg_cap: int | None = None):
         """Feature grouping / slot passes / grid for a level with max_slots built nodes.
         Shallow levels use 64 KB / 512-thread workgroups (2 per CU); levels
         that would need >= 4 feature groups switch to 128 KB / 1024 threads
-        (1 per CU) so each row chunk is re-read by fewer groups."""
-        key = max_slots
+        (1 per CU) so each row chunk is re-read by fewer groups.  fg_cap: widest
+        feature group (the batched loop's plans)."""
+        key = max_slots if fg_cap is None else (max_slots, fg_cap)
         if key in self.plans:
             return self.plans[key]
-        plan = self._choose(max_slots)
+        plan = self._choose(max_slots, fg_cap=fg_cap)
         self.plans[key] = plan
         return plan
 
-    def _choose(self, max_slots: int, units: int | None = None):
+    def _choose(self, max_slots: int, units: int | None = None, fg_cap: int | None = None):
         """plan_level's choice for ``units`` row units (default: this rank's)."""
         lo, hi = self.LDS_BUDGET, self.DEEP_LDS_BUDGET
-        plan = self._plan(max_slots, lo, self.THREADS, units)
+        plan = self._plan(max_slots, lo, self.THREADS, units, fg_cap=fg_cap)
         if hi > lo and plan["n_groups"] >= self.DEEP_MIN_GROUPS:
-            deep = self._plan(max_slots, hi, 1024, units)
+            deep = self._plan(max_slots, hi, 1024, units, fg_cap=fg_cap)
             if deep["n_groups"] < plan["n_groups"] or deep["passes"] < plan["passes"]:
                 plan = deep
         return plan
@@ -604,6 +620,15 @@ class HipTreeBuilder:
             l0_copies = d == 0 and grad_fuse is None and self.L0_COPIES in (4, 8)
             if l0_copies:
                 plan = self.plan_l0()
+            # level 0's hist_build launch takes the batched loop, in groups of <=
+            # HIST_FG_MAX planes (the plain last level measured slower with it - its
+            # time is the LDS atomics' - and keeps the feature loop:
+            # profiles/r14/hist_stream_ab.txt)
+            batch = (self.HIST_BATCH and d == 0 and grad_fuse is None and self.ROWS_PER_LANE == 16
+                     and plan["passes"] == 1)
+            if batch and plan["fg"] > self.HIST_FG_MAX:
+                plan = (self.plan_l0(self.HIST_FG_MAX) if l0_copies
+                        else self.plan_level(max_slots, self.HIST_FG_MAX))
             built = self._buf("built", max_slots * self.per_node, torch.int64)
             full_cur = None if last else self._buf(f"full{cur}", max_nodes * self.per_node, torch.int64)
             sp.depth = d
@@ -730,7 +755,8 @@ class HipTreeBuilder:
                             P(self.slot16), P(self.pk),
                             ((6 if pk_boost else 1 + (2 if self.pk32 else 0)) if d == 0
                              else 2 + (2 if self.pk32 else 0))
-                            + ({8: 16, 4: 32}.get(self.L0_COPIES, 0) if l0_copies else 0),
+                            + ({8: 16, 4: 32}.get(self.L0_COPIES, 0) if l0_copies else 0)
+                            + (128 if batch else 0),
                             P(partials), P(joint), P(plane_src), st),
                             "hist_build")
                 with T("hist_reduce"):
