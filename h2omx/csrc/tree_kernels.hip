@@ -468,19 +468,6 @@ __device__ __forceinline__ void wave_lds_sync() {
 // group and slot pass reads the previous ids).  Rows of nodes that stopped
 // splitting retire as ~gid; their exact leaf sums are added by the tree's
 // final partition (all-rows mode).  Saves one streaming pass per level.
-// CMP (deeper levels, PKM 2/4, ROWS 16): LDS-staged wave compaction.  A
-// ds_add_u64 wave-instruction costs ~14 CU-cycles whatever its lane mask
-// (bench_micro/lds_mask.hip: 14.3 cycles with 12 % of lanes active, 17.3 with
-// all), so issuing one atomic per (row position, feature) wastes most of the
-// LDS pipe on levels where only the smaller children (<= 50 % of the rows)
-// are built.  Here each wave (1024 consecutive rows) ranks its live rows with
-// five bit-plane ballots, writes them as 16-bit entries (row offset | slot <<
-// 10) into a per-wave 2 KB LDS area and reads them back transposed (lane j:
-// entries j, j + 64, ...).  Per feature the 1 KB code tile is stored to that
-// area with one ds_write_b128 per lane (the same coalesced column load as the
-// plain path) and every atomic then carries 64 live rows: ceil(live / 64)
-// full-mask atomics instead of 16 mostly-empty ones.  Same adds, same
-// integer histograms (bit-identical).
 struct GradParams {
   int dist;
   int apply_tree;      // add the leaf values of `tree` to F first
@@ -930,12 +917,14 @@ __device__ void level_fin_records(const FeatBest* __restrict__ fbest, const int*
   level_finalize_body(ctl, p, nbt, lv);
 }
 
-constexpr int CMP_STAGE_BYTES = 2048;   // per wave
 // Feature loop of the histogram kernel: one trip handles HB_PF features and
 // issues the next trip's code loads, 16 atomics per feature before the loop's
 // back edge drains them (s_waitcnt vmcnt(0)) - at most ~1.5 loads in flight
 // per lane whatever HB_PF is, one exposed memory round trip per trip.  The
 // batched loop below (FG_MAX) replaces it where the engine selects it.
+// (The depth stays a constant with its one-trip loops: written out for depth 1
+// the feature loop is rotated differently and the 1.375M-row shard and
+// xgboost-airlines measured 0.3-0.5 % slower, profiles/r15/hist_build_refactor.txt)
 constexpr int HB_PF = 1;
 // Batched loop (mode bit 7, engine.py HIST_BATCH): the level-0 kernels (PKM
 // 1 / 3 / 6, one slot, 16-row units) issue a row unit's packed-row loads and the
@@ -950,6 +939,8 @@ constexpr int HB_PF = 1;
 // cost alone was not measured; the 1.375M-row shard, whose level 0 runs such
 // groups, is faster with the loop than without (16.6 vs 19.0 us).
 constexpr int FG_MAX = 8;
+// rows per lane and row unit (HipTreeBuilder.ROWS_PER_LANE; the launcher takes no other)
+constexpr int ROWS = 16;
 
 // 16-bit packed row (int16 G_q << 16 | uint16 S_q) -> the 64-bit histogram addend
 __device__ __forceinline__ unsigned long long pk_widen(uint32_t pw) {
@@ -971,7 +962,7 @@ __device__ __forceinline__ unsigned long long pk_quantise(float gv, float sv, fl
 // 16 lanes of a ds_add_u64 group then hit at most two addresses per bank pair
 // (bench_micro/lds_atomics.hip: random bins 14.4 CU-cycles per wave-atomic,
 // conflict-free 7.3), at COP x the LDS per feature (fewer features per group)
-// NID16 (fused-routing levels): the previous / next node ids are int16 streams
+// ROUTE (fused-routing levels): the previous / next node ids are int16 streams
 // (2 bytes a row each way instead of 4; padding rows hold INT16_MIN)
 // Histogram planes: the kernel builds F planes of valid-bin counts nvb[]; with
 // a plane table (plane_src, one rank: engine.py BUNDLE) plane p reads feature
@@ -980,7 +971,7 @@ __device__ __forceinline__ unsigned long long pk_quantise(float gv, float sv, fl
 // nvb = NBT - 1: one full-width slice).  reduce_split marginalises the joint
 // rows back into per-feature rows.  The fused routing and the level prologue
 // read the split features' own planes of `codes` either way.
-template <int NBT, int ROWS, int PKM, bool ROUTE, bool CMP, int COP = 1, bool NID16 = false, bool BATCH = false>
+template <int NBT, int PKM, bool ROUTE, int COP = 1, bool BATCH = false>
 __global__ __launch_bounds__(1024) void hist_build_kernel(
     const uint8_t* __restrict__ codes, int64_t npad, const float* __restrict__ g, const float* __restrict__ s2,
     const int* __restrict__ nid, const NodeLink* __restrict__ link, const int* __restrict__ ctl,
@@ -1015,7 +1006,7 @@ __global__ __launch_bounds__(1024) void hist_build_kernel(
   if (!build && !route_w) return;
   const int f0 = group * fg;
   const int nf = min(fg, F - f0);
-  static_assert(COP == 1 || ((PKM == 1 || PKM == 3 || PKM == 6) && !ROUTE && !CMP), "copies: level-0 kernel only");
+  static_assert(COP == 1 || ((PKM == 1 || PKM == 3 || PKM == 6) && !ROUTE), "copies: level-0 kernel only");
   const int hist_elems = slot_cnt * fg * NBT;
   const int lane = threadIdx.x & 63;
   // codes of histogram plane f0 + fi (wave-uniform index: a scalar table load)
@@ -1050,7 +1041,7 @@ __global__ __launch_bounds__(1024) void hist_build_kernel(
   // batched loop: the planes' code bases and slice shapes, wave-uniform, once
   // per workgroup (entries past nf repeat the last plane: their loads are
   // issued - so every wait is a counted one - and never consumed)
-  static_assert(!BATCH || (!ROUTE && !CMP && (PKM == 1 || PKM == 3 || PKM == 6) && ROWS == 16),
+  static_assert(!BATCH || (!ROUTE && (PKM == 1 || PKM == 3 || PKM == 6)),
                 "batched loop: level 0 (one slot: the launcher checks)");
   constexpr int NQ = BATCH ? FG_MAX : 1;
   const uint8_t* pbase[NQ];
@@ -1069,13 +1060,7 @@ __global__ __launch_bounds__(1024) void hist_build_kernel(
 
   const int64_t units = npad / ROWS;
   const int64_t u0 = units * chunk / wgpg, u1 = units * (chunk + 1) / wgpg;
-  // CMP: waves step through the chunk together (64 consecutive units per wave
-  // step) so the ballots below see converged waves; tail lanes re-read the
-  // chunk's last unit and contribute no rows
-  const int64_t ustart = CMP ? u0 + (threadIdx.x & ~63) : u0 + threadIdx.x;
-  for (int64_t uu = ustart; uu < u1; uu += blockDim.x) {
-    const bool inb = !CMP || uu + lane < u1;
-    const int64_t u = CMP ? (inb ? uu + lane : u1 - 1) : uu;
+  for (int64_t u = u0 + threadIdx.x; u < u1; u += blockDim.x) {
     const int64_t r0 = u * ROWS;
     int s[ROWS];
     bool any = false;
@@ -1086,7 +1071,7 @@ __global__ __launch_bounds__(1024) void hist_build_kernel(
         // no node-id stream to read (boost_update no longer resets it)
 #pragma unroll
         for (int k = 0; k < ROWS; ++k) nn[k] = (r0 + k < n_rows) ? 0 : INT32_MIN;
-      } else if constexpr (NID16) {
+      } else {
         const short* n16 = reinterpret_cast<const short*>(nid);
 #pragma unroll
         for (int q = 0; q < ROWS / 8; ++q) {
@@ -1094,12 +1079,6 @@ __global__ __launch_bounds__(1024) void hist_build_kernel(
           const uint32_t w4[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
           for (int k = 0; k < 8; ++k) nn[8 * q + k] = (int)(short)(w4[k >> 1] >> (16 * (k & 1)));
-        }
-      } else {
-#pragma unroll
-        for (int q = 0; q < ROWS / 4; ++q) {
-          const int4 n4 = *reinterpret_cast<const int4*>(nid + r0 + 4 * q);
-          nn[4 * q] = n4.x; nn[4 * q + 1] = n4.y; nn[4 * q + 2] = n4.z; nn[4 * q + 3] = n4.w;
         }
       }
 #pragma unroll
@@ -1122,13 +1101,8 @@ __global__ __launch_bounds__(1024) void hist_build_kernel(
         }
         uint32_t cw[ROWS / 4];
         const uint8_t* cp = codes + (int64_t)pj.feat * npad + r0;
-        if constexpr (ROWS == 16) {
-          const uint4 c4 = *reinterpret_cast<const uint4*>(cp);
-          cw[0] = c4.x; cw[1] = c4.y; cw[2] = c4.z; cw[3] = c4.w;
-        } else {
-          const uint2 c2 = *reinterpret_cast<const uint2*>(cp);
-          cw[0] = c2.x; cw[1] = c2.y;
-        }
+        const uint4 c4 = *reinterpret_cast<const uint4*>(cp);
+        cw[0] = c4.x; cw[1] = c4.y; cw[2] = c4.z; cw[3] = c4.w;
         const int sl_l = (int)(short)(pj.pad & 0xFFFF), sl_r = pj.pad >> 16;
 #pragma unroll
         for (int k = 0; k < ROWS; ++k) {
@@ -1148,21 +1122,15 @@ __global__ __launch_bounds__(1024) void hist_build_kernel(
         any |= (sl >= 0);
       }
       if (route_w) {
-        if constexpr (NID16) {
-          short* o16 = reinterpret_cast<short*>(nid_out);
+        short* o16 = reinterpret_cast<short*>(nid_out);
 #pragma unroll
-          for (int q = 0; q < ROWS / 8; ++q) {
-            uint32_t w4[4];
+        for (int q = 0; q < ROWS / 8; ++q) {
+          uint32_t w4[4];
 #pragma unroll
-            for (int k = 0; k < 4; ++k)
-              w4[k] = ((uint32_t)(uint16_t)max(nx[8 * q + 2 * k], -32768)) |
-                      ((uint32_t)(uint16_t)max(nx[8 * q + 2 * k + 1], -32768) << 16);
-            *reinterpret_cast<uint4*>(o16 + r0 + 8 * q) = make_uint4(w4[0], w4[1], w4[2], w4[3]);
-          }
-        } else {
-#pragma unroll
-          for (int q = 0; q < ROWS / 4; ++q)
-            *reinterpret_cast<int4*>(nid_out + r0 + 4 * q) = make_int4(nx[4 * q], nx[4 * q + 1], nx[4 * q + 2], nx[4 * q + 3]);
+          for (int k = 0; k < 4; ++k)
+            w4[k] = ((uint32_t)(uint16_t)max(nx[8 * q + 2 * k], -32768)) |
+                    ((uint32_t)(uint16_t)max(nx[8 * q + 2 * k + 1], -32768) << 16);
+          *reinterpret_cast<uint4*>(o16 + r0 + 8 * q) = make_uint4(w4[0], w4[1], w4[2], w4[3]);
         }
       }
     } else if constexpr (PKM == 2 || PKM == 4) {
@@ -1204,11 +1172,7 @@ __global__ __launch_bounds__(1024) void hist_build_kernel(
         }
       }
     }
-    if constexpr (CMP) {
-      if (__ballot(any && inb) == 0ull) continue;   // wave-uniform
-    } else {
-      if (!any) continue;
-    }
+    if (!any) continue;
     if constexpr (BATCH) {
       uint32_t live = 0;   // rows in the histogram
 #pragma unroll
@@ -1315,20 +1279,12 @@ __global__ __launch_bounds__(1024) void hist_build_kernel(
     // overlaps the (g, s) loads / gradient chain instead of following it
     uint32_t pf[HB_PF][ROWS / 4];
     auto load_codes = [&](int fi, uint32_t* cw) {
-      const uint8_t* cp = plane_codes(fi) + r0;
-      if constexpr (ROWS == 16) {
-        const uint4 c4 = *reinterpret_cast<const uint4*>(cp);
-        cw[0] = c4.x; cw[1] = c4.y; cw[2] = c4.z; cw[3] = c4.w;
-      } else {
-        const uint2 c2 = *reinterpret_cast<const uint2*>(cp);
-        cw[0] = c2.x; cw[1] = c2.y;
-      }
+      const uint4 c4 = *reinterpret_cast<const uint4*>(plane_codes(fi) + r0);
+      cw[0] = c4.x; cw[1] = c4.y; cw[2] = c4.z; cw[3] = c4.w;
     };
-    if constexpr (!CMP) {
 #pragma unroll
-      for (int q = 0; q < HB_PF; ++q)
-        if (q < nf) load_codes(q, pf[q]);
-    }
+    for (int q = 0; q < HB_PF; ++q)
+      if (q < nf) load_codes(q, pf[q]);
     unsigned long long pk[ROWS];
     if constexpr (PKM == 2) {
 #pragma unroll
@@ -1416,84 +1372,6 @@ __global__ __launch_bounds__(1024) void hist_build_kernel(
         *reinterpret_cast<uint4*>(pk32 + r0 + 4 * q) = make_uint4(pw[0], pw[1], pw[2], pw[3]);
       }
     }
-    }
-    if constexpr (CMP) {
-      static_assert(ROWS == 16 && (PKM == 2 || PKM == 4), "compaction: 16-row units reading stored rows");
-      uint32_t m = 0;
-#pragma unroll
-      for (int r = 0; r < ROWS; ++r)
-        if (inb && s[r] >= 0 && pk[r] != 0ull) m |= 1u << r;
-      // exclusive rank of this lane's first live row in the wave, from the
-      // bit planes of the per-lane counts (0..16): five ballots, no LDS
-      const uint32_t cnt = __popc(m);
-      const unsigned long long lt = (1ull << lane) - 1ull;
-      int excl = 0, total = 0;
-#pragma unroll
-      for (int bit = 0; bit < 5; ++bit) {
-        const unsigned long long bm = __ballot((cnt >> bit) & 1u);
-        excl += __popcll(bm & lt) << bit;
-        total += __popcll(bm) << bit;
-      }
-      if (total == 0) continue;
-      uint16_t* st16 = reinterpret_cast<uint16_t*>(lds64 + hist_elems) + (threadIdx.x >> 6) * (CMP_STAGE_BYTES / 2);
-      int j = excl;
-#pragma unroll
-      for (int r = 0; r < ROWS; ++r)
-        if ((m >> r) & 1u) st16[j++] = (uint16_t)((lane * ROWS + r) | (s[r] << 10));
-      const int niter = (total + 63) >> 6;
-      const int64_t tile0 = (uu)*ROWS;   // first row of this wave's tile
-      // entry i of this lane is live iff i * 64 + lane < total (every 16-bit
-      // pattern is a valid entry: offset 1023 in slot 63 is 0xFFFF)
-      uint32_t ent[ROWS];
-      unsigned long long pkc[ROWS];
-#pragma unroll
-      for (int i = 0; i < ROWS; ++i) {
-        ent[i] = 0u;
-        if (i * 64 + lane < total) ent[i] = st16[i * 64 + lane];
-      }
-#pragma unroll
-      for (int i = 0; i < ROWS; ++i) {
-        pkc[i] = 0ull;
-        if (i * 64 + lane < total) {
-          const int64_t row = tile0 + (ent[i] & 1023u);
-          if constexpr (PKM == 2) {
-            pkc[i] = pk_buf[row];
-          } else {
-            const uint32_t pw = reinterpret_cast<const uint32_t*>(pk_buf)[row];
-            pkc[i] = ((unsigned long long)(uint32_t)(int)(short)(pw >> 16) << 32) | (unsigned long long)(pw & 0xFFFFu);
-          }
-        }
-      }
-      // the entries are in registers before the code tiles overwrite the area
-      __asm__ volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      uint8_t* stc = reinterpret_cast<uint8_t*>(st16);
-      uint4 pf[HB_PF];
-#pragma unroll
-      for (int q = 0; q < HB_PF; ++q)
-        if (q < nf) pf[q] = *reinterpret_cast<const uint4*>(plane_codes(q) + r0);
-      for (int fb = 0; fb < nf; fb += HB_PF) {
-#pragma unroll
-        for (int q = 0; q < HB_PF; ++q) {
-          const int fi = fb + q;
-          if (fi < nf) {
-            *reinterpret_cast<uint4*>(stc + lane * ROWS) = pf[q];
-            if (fi + HB_PF < nf) pf[q] = *reinterpret_cast<const uint4*>(plane_codes(fi + HB_PF) + r0);
-            const int width = width_s[fi], rep = rep_s[fi];
-            const int copy_off = (rep > 1) ? (lane % rep) * width : 0;
-            const int na_slot = (rep > 1) ? width - 1 : NBT - 1;   // see the fold below
-            unsigned long long* hb = lds64 + fi * NBT + copy_off;
-#pragma unroll
-            for (int i = 0; i < ROWS; ++i) {
-              if (i < niter && i * 64 + lane < total) {
-                int bin = stc[ent[i] & 1023u];
-                if (bin == NBT - 1) bin = na_slot;
-                atomicAdd(hb + (int)(ent[i] >> 10) * fg * NBT + bin, pkc[i]);
-              }
-            }
-          }
-        }
-      }
-      continue;
     }
     // per-row slot offset into the histogram (-1: nothing to add), once per unit
     int so[ROWS];
@@ -2754,22 +2632,6 @@ __global__ __launch_bounds__(256) void partition_kernel(const uint8_t* __restric
   }
 }
 
-// leaf_acc[j] += sum over the partition slabs (one 256-thread block per j).
-__global__ __launch_bounds__(256) void leaf_reduce_kernel(const unsigned long long* __restrict__ slab, int n_slabs,
-                                                          int width, unsigned long long* __restrict__ leaf_acc) {
-  __shared__ unsigned long long red[256];
-  const int j = blockIdx.x;
-  unsigned long long v = 0ull;
-  for (int s = threadIdx.x; s < n_slabs; s += blockDim.x) v += slab[(int64_t)s * width + j];
-  red[threadIdx.x] = v;
-  __syncthreads();
-  for (int off = 128; off > 0; off >>= 1) {
-    if (threadIdx.x < off) red[threadIdx.x] += red[threadIdx.x + off];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0 && red[0]) leaf_acc[j] += red[0];
-}
-
 // ---------------------------------------------------------------------------
 // K2 + K7: apply the finished tree to the margins and compute the next
 // tree's gradients, bagging weights and reset the row->node ids, fused in
@@ -2813,7 +2675,7 @@ __global__ __launch_bounds__(256) void boost_update_kernel(float* __restrict__ F
                                                            const short* __restrict__ nid16) {
   if (ring != nullptr) {
     // graph replay: the applied tree also goes to ring slot (tree_ctr - ctr_off)
-    // mod ring_n (tree_archive folded into this launch)
+    // mod ring_n (the archive copy, folded into this launch)
     const int slot = (int)(((unsigned)(tree_ctr[0] - ctr_off)) % (unsigned)ring_n);
     uint4* dst = ring + (int64_t)slot * arch_n16;
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < arch_n16; i += gridDim.x * blockDim.x) dst[i] = arch_src[i];
@@ -3033,44 +2895,6 @@ __global__ __launch_bounds__(256) void tree_begin_kernel(const unsigned int* __r
   tree_begin_scales(stat_max, mode, qg, qsr, qs, ctl0, link0, row_base, tree_index, tree_ctr);
 }
 
-// Exact per-leaf (G, H, W) sums after the last partition: every row carries
-// nid = ~leaf_gid.  int64 fixed point -> deterministic; LDS-privatised when
-// the tree capacity fits (depth <= 10), global atomics otherwise.
-__global__ __launch_bounds__(256) void leaf_stats_kernel(const int* __restrict__ nid, const float* __restrict__ g,
-                                                         const float* __restrict__ h, const float* __restrict__ w,
-                                                         int64_t n, const double* __restrict__ qs, int cap,
-                                                         unsigned long long* __restrict__ acc) {
-  extern __shared__ __attribute__((aligned(16))) unsigned long long lacc[];
-  const bool use_lds = cap <= 2048;
-  if (use_lds) {
-    for (int j = threadIdx.x; j < 3 * cap; j += blockDim.x) lacc[j] = 0ull;
-    __syncthreads();
-  }
-  const double lg = qs[4], lh = qs[5], lw = qs[6];
-  for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < n; r += (int64_t)gridDim.x * blockDim.x) {
-    const int leaf = ~nid[r];
-    if (leaf < 0 || leaf >= cap) continue;
-    const float wv = w ? w[r] : 1.0f;
-    if (wv == 0.0f) continue;
-    const long long gq = __float2int_rn(g[r] * (float)lg), hq = __float2int_rn(h[r] * (float)lh),
-                    wq = __float2int_rn(wv * (float)lw);
-    if (use_lds) {  // separate call sites keep ds_add_u64 (see partition_kernel)
-      atomicAdd(lacc + 3 * leaf + 0, (unsigned long long)gq);
-      atomicAdd(lacc + 3 * leaf + 1, (unsigned long long)hq);
-      atomicAdd(lacc + 3 * leaf + 2, (unsigned long long)wq);
-    } else {
-      atomicAdd(acc + 3 * leaf + 0, (unsigned long long)gq);
-      atomicAdd(acc + 3 * leaf + 1, (unsigned long long)hq);
-      atomicAdd(acc + 3 * leaf + 2, (unsigned long long)wq);
-    }
-  }
-  if (use_lds) {
-    __syncthreads();
-    for (int j = threadIdx.x; j < 3 * cap; j += blockDim.x)
-      if (lacc[j]) atomicAdd(acc + j, lacc[j]);
-  }
-}
-
 // Overwrite every leaf's value with the Newton / mean step from the exact
 // leaf sums (and record its weight).
 __global__ __launch_bounds__(256) void leaf_finalize_kernel(const unsigned long long* __restrict__ acc,
@@ -3200,7 +3024,8 @@ __global__ __launch_bounds__(LEAF_P2P_THREADS) void leaf_finalize_p2p_kernel(
 // as H2O's gamma-based bounds do: depth of each reachable node (top-down),
 // subtree (G, H) sums (bottom-up), then [lo, hi] cut at the midpoint of the
 // clipped Newton child values (top-down), and every leaf is clamped into its
-// interval.  scratch: int dep[cap] | double SG[cap], SH[cap], LO[cap], HI[cap].
+// interval.  scratch: int dep[cap] | double SG[cap], SH[cap], LO[cap], HI[cap]
+// = round_up(4 * cap, 16) + 32 * cap bytes (engine.py sizes it by this formula).
 __global__ __launch_bounds__(1024) void mono_newton_kernel(const unsigned long long* __restrict__ acc,
                                                            const int* __restrict__ ctl_final,
                                                            const double* __restrict__ qs, SplitParams p,
@@ -3277,8 +3102,6 @@ __global__ __launch_bounds__(1024) void mono_newton_kernel(const unsigned long l
     __syncthreads();
   }
 }
-
-H2OMX_API int64_t h2omx_mono_scratch_bytes(int cap) { return (((int64_t)cap * 4 + 15) / 16) * 16 + (int64_t)cap * 32; }
 
 // ---------------------------------------------------------------------------
 // K8: score raw (unbinned) feature-major data with a tree ensemble.
@@ -3390,6 +3213,36 @@ static bool make_pro(LevelPro& lp, const void* fbest, const void* params, const 
   return copy_level_out(lp.lv, level_out);
 }
 
+// What the mode word and the entry point select of hist_build_kernel, and the
+// one list of the combinations that are compiled: per bin width the 13
+// feature-loop kernels (PKM 0 .. 6, level 0 in 1 / 4 / 8 lane copies), the 9
+// batched level-0 kernels and the 2 routed ones.  nullptr: not a combination.
+struct HistCfg {
+  int pkm, cop;
+  bool route, batch;
+};
+using HistKernel = decltype(&hist_build_kernel<32, 0, false>);
+template <int NBT>
+static HistKernel hist_build_pick(const HistCfg& c) {
+#define HB_CASE(M, RT, CP, B) \
+  if (c.pkm == M && c.route == RT && c.cop == CP && c.batch == B) return hist_build_kernel<NBT, M, RT, CP, B>
+#define HB_LEVEL0(M)                                                                   \
+  HB_CASE(M, false, 1, false); HB_CASE(M, false, 4, false); HB_CASE(M, false, 8, false); \
+  HB_CASE(M, false, 1, true); HB_CASE(M, false, 4, true); HB_CASE(M, false, 8, true)
+  HB_CASE(0, false, 1, false);
+  HB_LEVEL0(1);
+  HB_LEVEL0(3);
+  HB_LEVEL0(6);
+  HB_CASE(2, false, 1, false);
+  HB_CASE(4, false, 1, false);
+  HB_CASE(5, false, 1, false);
+  HB_CASE(2, true, 1, false);
+  HB_CASE(4, true, 1, false);
+#undef HB_LEVEL0
+#undef HB_CASE
+  return nullptr;
+}
+
 static int hist_build_launch(const uint8_t* codes, int64_t npad, const float* g, const float* s2, const int* nid,
                              const void* link, const int* ctl, const int* nvb, const double* qscale, int salt,
                              int F, int nbt, int fg, int n_groups, int wgpg, int slot_lo, int slot_cnt,
@@ -3410,146 +3263,54 @@ static int hist_build_launch(const uint8_t* codes, int64_t npad, const float* g,
   if (lpp && (!route || !writer || lpz.fbest == nullptr || lpz.lv.nsplit == nullptr || lpz.lv.ctl_next != ctl ||
               (const void*)lpz.lv.part != part_prev))
     return kBadArg;
-  // pkm bit 3: wave-compacted atomics (CMP; stored rows, 16-row units, <= 64 slots per pass)
-  const bool cmp = (pkm & 8) != 0;
-  // pkm bit 4 / 5: level-0 histograms in 8 / 4 interleaved lane copies (PKM 1 / 3 only)
-  const int cop = (pkm & 16) ? 8 : ((pkm & 32) ? 4 : 1);
-  // pkm bit 6: int16 node-id streams (routed levels only)
-  const bool nid16 = (pkm & 64) != 0;
-  // pkm bit 7: batched loop (FG_MAX) where the kernel has one: level 0 (pkm 1 / 3 / 6, one slot, 16-row units),
-  // groups of <= FG_MAX planes; anything else drops the bit and keeps the feature loop
-  bool batch = (pkm & 128) != 0;
-  pkm &= 7;
-  if (route || cmp || (pkm != 1 && pkm != 3 && pkm != 6) || fg > FG_MAX || rows_per_lane != 16 || slot_cnt != 1)
-    batch = false;
-  if (nid16 && (!route || cmp || rows_per_lane != 16)) return kBadArg;
-  if (cop > 1 && ((pkm != 1 && pkm != 3 && pkm != 6) || route || cmp)) return kBadArg;
+  // the mode word (engine.py hist_mode): bits 0-2 PKM; bit 3 unused (it selected a wave-compacted variant that
+  // measured slower, ROADMAP round 3); bits 4 / 5 level-0 histograms in 8 / 4 interleaved lane copies (PKM 1 /
+  // 3 / 6 only); bit 6 int16 node-id streams (every routed level, no other); bit 7 the batched loop (FG_MAX)
+  // where the kernel has one: level 0 (PKM 1 / 3 / 6, one slot), groups of <= FG_MAX planes - anything else
+  // drops the bit and keeps the feature loop
+  if (pkm & 8) return kBadArg;
+  if (rows_per_lane != ROWS) return kBadArg;
+  HistCfg c;
+  c.pkm = pkm & 7;
+  c.route = route;
+  c.cop = (pkm & 16) ? 8 : ((pkm & 32) ? 4 : 1);
+  const bool level0 = c.pkm == 1 || c.pkm == 3 || c.pkm == 6;
+  c.batch = (pkm & 128) != 0 && !route && level0 && fg <= FG_MAX && slot_cnt == 1;
+  if (((pkm & 64) != 0) != route) return kBadArg;
+  pkm = c.pkm;
+  if (c.cop > 1 && (!level0 || route)) return kBadArg;
   // pkm 6: level 0 reading the packed rows boost_update wrote (implicit root)
-  if (pkm == 6 && (nid != nullptr || route || cmp || pk_buf == nullptr)) return kBadArg;
-  if (cmp && ((pkm != 2 && pkm != 4) || rows_per_lane != 16 || slot_cnt > 64)) return kBadArg;
+  if (pkm == 6 && (nid != nullptr || route || pk_buf == nullptr)) return kBadArg;
   if (route && (ctl_prev == nullptr || nid_out == nullptr || nid_out == nid || (pkm != 2 && pkm != 4)))
     return kBadArg;
   const PartInfo* pp = reinterpret_cast<const PartInfo*>(part_prev);
   if (wgpg % 8 != 0 || npad % 16 != 0 || fg > 256 || threads % 64 != 0 || threads > 1024 || threads < fg)
     return kBadArg;
-  if (pkm < 0 || pkm > 6 || (pkm > 0 && pk_buf == nullptr) || ((pkm == 2 || pkm == 4) && !route && slot16 == nullptr))
+  if (pkm > 6 || (pkm > 0 && pk_buf == nullptr) || ((pkm == 2 || pkm == 4) && !route && slot16 == nullptr))
     return kBadArg;
-  // fused gradient level: implicit root (no node ids), 32-bit packed rows, no compaction / routing
-  if ((pkm == 5) != (gfp != nullptr) || (pkm == 5 && (nid != nullptr || route || cmp || gfz.F == nullptr ||
+  // fused gradient level: implicit root (no node ids), no routing
+  if ((pkm == 5) != (gfp != nullptr) || (pkm == 5 && (nid != nullptr || route || gfz.F == nullptr ||
                                                       gfz.y == nullptr || gfz.g == nullptr || gfz.h == nullptr ||
                                                       (gfz.apply && (gfz.nid == nullptr || gfz.tree == nullptr)))))
     return kBadArg;
-  const int64_t units = npad / rows_per_lane;
-  if ((units + wgpg - 1) / wgpg * rows_per_lane > ROWS_CAP) return kBadArg;  // fixed-point headroom
-  const size_t lds = (size_t)slot_cnt * fg * nbt * cop * sizeof(unsigned long long) +
-                     (cmp ? (size_t)(threads / 64) * CMP_STAGE_BYTES : 0);
+  const int64_t units = npad / ROWS;
+  if ((units + wgpg - 1) / wgpg * ROWS > ROWS_CAP) return kBadArg;  // fixed-point headroom
+  const size_t lds = (size_t)slot_cnt * fg * nbt * c.cop * sizeof(unsigned long long);
   if (lds > 156 * 1024) return kBadArg;
   const int grid = n_groups * wgpg;
   const NodeLink* lk = reinterpret_cast<const NodeLink*>(link);
-#define LAUNCH_HBK(NB, R, M, RT, C)                                                                           \
-  hipLaunchKernelGGL((hist_build_kernel<NB, R, M, RT, C>), dim3(grid), dim3(threads), lds, stream, codes, npad, \
-                     g, s2, nid, lk, ctl, nvb, qscale, (uint32_t)salt, F, fg, n_groups, wgpg, slot_lo, slot_cnt,  \
-                     slot16, pk_buf, partials, pp, ctl_prev, nid_out, writer, gfz, lpz, joint, plane_src)
-#define LAUNCH_HBKC(NB, R, M, CP)                                                                                \
-  hipLaunchKernelGGL((hist_build_kernel<NB, R, M, false, false, CP>), dim3(grid), dim3(threads), lds, stream, codes, \
-                     npad, g, s2, nid, lk, ctl, nvb, qscale, (uint32_t)salt, F, fg, n_groups, wgpg, slot_lo,        \
-                     slot_cnt, slot16, pk_buf, partials, pp, ctl_prev, nid_out, writer, gfz, lpz, joint, plane_src)
-#define LAUNCH_HBK16(NB, M)                                                                                      \
-  hipLaunchKernelGGL((hist_build_kernel<NB, 16, M, true, false, 1, true>), dim3(grid), dim3(threads), lds, stream, \
-                     codes, npad, g, s2, nid, lk, ctl, nvb, qscale, (uint32_t)salt, F, fg, n_groups, wgpg, slot_lo,    \
-                     slot_cnt, slot16, pk_buf, partials, pp, ctl_prev, nid_out, writer, gfz, lpz, joint, plane_src)
-#define LAUNCH_HBB(NB, M, CP)                                                                                    \
-  hipLaunchKernelGGL((hist_build_kernel<NB, 16, M, false, false, CP, false, true>), dim3(grid), dim3(threads), lds, \
-                     stream, codes, npad, g, s2, nid, lk, ctl, nvb, qscale, (uint32_t)salt, F, fg, n_groups, wgpg,    \
-                     slot_lo, slot_cnt, slot16, pk_buf, partials, pp, ctl_prev, nid_out, writer, gfz, lpz, joint,     \
-                     plane_src)
-#define LAUNCH_HBATCH(NB)                                      \
-  do {                                                        \
-    if (pkm == 1 && cop == 8) LAUNCH_HBB(NB, 1, 8);            \
-    else if (pkm == 1 && cop == 4) LAUNCH_HBB(NB, 1, 4);       \
-    else if (pkm == 1) LAUNCH_HBB(NB, 1, 1);                   \
-    else if (pkm == 3 && cop == 8) LAUNCH_HBB(NB, 3, 8);       \
-    else if (pkm == 3 && cop == 4) LAUNCH_HBB(NB, 3, 4);       \
-    else if (pkm == 3) LAUNCH_HBB(NB, 3, 1);                   \
-    else if (cop == 8) LAUNCH_HBB(NB, 6, 8);                   \
-    else if (cop == 4) LAUNCH_HBB(NB, 6, 4);                   \
-    else LAUNCH_HBB(NB, 6, 1);                                 \
-  } while (0)
-#define LAUNCH_HB(NB, R)                                            \
-  do {                                                             \
-    if (pkm == 0) LAUNCH_HBK(NB, R, 0, false, false);               \
-    else if (pkm == 1 && cop == 8) LAUNCH_HBKC(NB, R, 1, 8);        \
-    else if (pkm == 3 && cop == 8) LAUNCH_HBKC(NB, R, 3, 8);        \
-    else if (pkm == 1 && cop == 4) LAUNCH_HBKC(NB, R, 1, 4);        \
-    else if (pkm == 3 && cop == 4) LAUNCH_HBKC(NB, R, 3, 4);        \
-    else if (pkm == 6 && cop == 8) LAUNCH_HBKC(NB, R, 6, 8);        \
-    else if (pkm == 6 && cop == 4) LAUNCH_HBKC(NB, R, 6, 4);        \
-    else if (pkm == 6) LAUNCH_HBK(NB, R, 6, false, false);          \
-    else if (pkm == 1) LAUNCH_HBK(NB, R, 1, false, false);          \
-    else if (pkm == 2 && route) LAUNCH_HBK(NB, R, 2, true, false);  \
-    else if (pkm == 2) LAUNCH_HBK(NB, R, 2, false, false);          \
-    else if (pkm == 3) LAUNCH_HBK(NB, R, 3, false, false);          \
-    else if (pkm == 5) LAUNCH_HBK(NB, R, 5, false, false);          \
-    else if (route) LAUNCH_HBK(NB, R, 4, true, false);              \
-    else LAUNCH_HBK(NB, R, 4, false, false);                        \
-  } while (0)
-#define LAUNCH_HBCMP(NB)                                             \
-  do {                                                              \
-    if (pkm == 2 && route) LAUNCH_HBK(NB, 16, 2, true, true);        \
-    else if (pkm == 2) LAUNCH_HBK(NB, 16, 2, false, true);           \
-    else if (route) LAUNCH_HBK(NB, 16, 4, true, true);               \
-    else LAUNCH_HBK(NB, 16, 4, false, true);                         \
-  } while (0)
-  if (batch) {
-    switch (nbt) {
-      case 32: LAUNCH_HBATCH(32); break;
-      case 64: LAUNCH_HBATCH(64); break;
-      case 128: LAUNCH_HBATCH(128); break;
-      case 256: LAUNCH_HBATCH(256); break;
-      default: return kBadArg;
-    }
-  } else if (cmp) {
-    switch (nbt) {
-      case 32: LAUNCH_HBCMP(32); break;
-      case 64: LAUNCH_HBCMP(64); break;
-      case 128: LAUNCH_HBCMP(128); break;
-      case 256: LAUNCH_HBCMP(256); break;
-      default: return kBadArg;
-    }
-  } else if (nid16) {
-    switch (nbt) {
-      case 32: if (pkm == 2) LAUNCH_HBK16(32, 2); else LAUNCH_HBK16(32, 4); break;
-      case 64: if (pkm == 2) LAUNCH_HBK16(64, 2); else LAUNCH_HBK16(64, 4); break;
-      case 128: if (pkm == 2) LAUNCH_HBK16(128, 2); else LAUNCH_HBK16(128, 4); break;
-      case 256: if (pkm == 2) LAUNCH_HBK16(256, 2); else LAUNCH_HBK16(256, 4); break;
-      default: return kBadArg;
-    }
-  } else if (rows_per_lane == 16) {
-    switch (nbt) {
-      case 32: LAUNCH_HB(32, 16); break;
-      case 64: LAUNCH_HB(64, 16); break;
-      case 128: LAUNCH_HB(128, 16); break;
-      case 256: LAUNCH_HB(256, 16); break;
-      default: return kBadArg;
-    }
-  } else if (rows_per_lane == 8) {
-    switch (nbt) {
-      case 32: LAUNCH_HB(32, 8); break;
-      case 64: LAUNCH_HB(64, 8); break;
-      case 128: LAUNCH_HB(128, 8); break;
-      case 256: LAUNCH_HB(256, 8); break;
-      default: return kBadArg;
-    }
-  } else {
-    return kBadArg;
+  HistKernel kern = nullptr;
+  switch (nbt) {
+    case 32: kern = hist_build_pick<32>(c); break;
+    case 64: kern = hist_build_pick<64>(c); break;
+    case 128: kern = hist_build_pick<128>(c); break;
+    case 256: kern = hist_build_pick<256>(c); break;
+    default: return kBadArg;
   }
-#undef LAUNCH_HB
-#undef LAUNCH_HBATCH
-#undef LAUNCH_HBB
-#undef LAUNCH_HBK16
-#undef LAUNCH_HBCMP
-#undef LAUNCH_HBK
-#undef LAUNCH_HBKC
+  if (kern == nullptr) return kBadArg;
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), lds, stream, codes, npad, g, s2, nid, lk, ctl, nvb, qscale,
+                     (uint32_t)salt, F, fg, n_groups, wgpg, slot_lo, slot_cnt, slot16, pk_buf, partials, pp, ctl_prev,
+                     nid_out, writer, gfz, lpz, joint, plane_src);
   return launch_status();
 }
 
@@ -3943,26 +3704,6 @@ H2OMX_API int h2omx_boost_update(float* F, const float* y, const float* wobs, in
   return launch_status();
 }
 
-// Graph replay: the finished tree -> slot (tree_ctr - 1) mod R of a ring of R
-// tree heaps (tree_begin advanced the counter), so a replayed step needs no
-// host-side snapshot copy per tree (boost.TreeGraph freezes the ring every R trees)
-__global__ __launch_bounds__(256) void tree_archive_kernel(const uint4* __restrict__ src, int n16,
-                                                           uint4* __restrict__ ring, int R,
-                                                           const int* __restrict__ tree_ctr) {
-  const int slot = (int)(((unsigned)(tree_ctr[0] - 1)) % (unsigned)R);
-  uint4* dst = ring + (int64_t)slot * n16;
-  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n16; i += gridDim.x * blockDim.x) dst[i] = src[i];
-}
-
-H2OMX_API int h2omx_tree_archive(const void* tree, int64_t bytes, void* ring, int R, const int* tree_ctr,
-                                 hipStream_t stream) {
-  if (bytes % 16 != 0 || R < 1 || tree_ctr == nullptr) return kBadArg;
-  const int n16 = (int)(bytes / 16);
-  hipLaunchKernelGGL(tree_archive_kernel, dim3(grid_for(n16, 256, 64)), dim3(256), 0, stream,
-                     reinterpret_cast<const uint4*>(tree), n16, reinterpret_cast<uint4*>(ring), R, tree_ctr);
-  return launch_status();
-}
-
 H2OMX_API int h2omx_apply_tree(float* F, int64_t n, const int* nid, const void* tree, hipStream_t stream) {
   hipLaunchKernelGGL(apply_tree_kernel, dim3(grid_for(n, 256)), dim3(256), 0, stream, F, n, nid,
                      reinterpret_cast<const TreeNode*>(tree));
@@ -4006,22 +3747,7 @@ H2OMX_API int h2omx_tree_begin(const unsigned int* stat_max, int mode, int max_r
   return launch_status();
 }
 
-H2OMX_API int h2omx_leaf_stats(const int* nid, const float* g, const float* h, const float* w, int64_t n,
-                               const double* qscale, int cap, unsigned long long* acc, hipStream_t stream) {
-  const size_t lds = cap <= 2048 ? (size_t)cap * 3 * sizeof(unsigned long long) : 0;
-  hipLaunchKernelGGL(leaf_stats_kernel, dim3(grid_for(n, 256, 1024)), dim3(256), lds, stream, nid, g, h, w, n, qscale,
-                     cap, acc);
-  return launch_status();
-}
-
 H2OMX_API int h2omx_partition_blocks() { return PARTITION_BLOCKS; }
-
-H2OMX_API int h2omx_leaf_reduce(const unsigned long long* slab, int n_slabs, int cap, unsigned long long* leaf_acc,
-                                hipStream_t stream) {
-  if (n_slabs <= 0) return kOk;
-  hipLaunchKernelGGL(leaf_reduce_kernel, dim3(3 * cap), dim3(256), 0, stream, slab, n_slabs, 3 * cap, leaf_acc);
-  return launch_status();
-}
 
 H2OMX_API int h2omx_leaf_finalize(const unsigned long long* acc, const int* ctl_final, const double* qscale,
                                   const void* params, void* tree, int cap, hipStream_t stream) {
@@ -4070,7 +3796,7 @@ H2OMX_API int h2omx_leaf_finalize_p2p(const void* desc, unsigned long long* acc,
 }
 
 // leaf_finalize + (mode 0, Newton leaves, monotone constraints) the leaf-scale
-// interval pass; scratch of h2omx_mono_scratch_bytes(cap) bytes
+// interval pass; scratch: see mono_newton_kernel for its size
 H2OMX_API int h2omx_leaf_finalize_mono(const unsigned long long* acc, const int* ctl_final, const double* qscale,
                                        const void* params, void* tree, int cap, void* scratch, hipStream_t stream) {
   const SplitParams p = *reinterpret_cast<const SplitParams*>(params);

@@ -790,7 +790,7 @@ class TreeGraph:
     """
 
     # finished trees go to a device ring of RING slots inside the graph
-    # (tree_archive kernel); trees_dev holds views of the live ring until
+    # (boost_update copies them); trees_dev holds views of the live ring until
     # freeze() swaps them for views of one ring snapshot (every RING trees, and
     # whenever the trees are read)
     RING = 64

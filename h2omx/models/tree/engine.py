@@ -67,14 +67,22 @@ def tree_capacity(max_depth: int) -> int:
     return (1 << (max_depth + 1)) - 1
 
 
-class HipTreeBuilder:
-    """Builds one tree per call entirely with enqueued HIP kernels.
+# The mode word of h2omx_hist_build / _route / _route_fin (csrc/tree_kernels.hip,
+# hist_build_launch).  Bits 0-2, the packed-row mode PKM: 0 quantise (g, s2),
+# store nothing; 1 / 3 quantise and store 64- / 32-bit packed rows (level 0);
+# 2 / 4 read stored 64- / 32-bit rows (deeper levels); 5 is h2omx_hist_build_grad's
+# own; 6 level 0 reading the 32-bit rows boost_update stored.
+HIST_COPIES = {8: 16, 4: 32}   # level-0 histograms in 8 / 4 interleaved lane copies
+HIST_NID16 = 64                # int16 node-id streams: every routed level
+HIST_BATCH_LOOP = 128          # the batched loop (level 0)
 
-    Per tree: quantisation scales from the gradient maxima (written by the
-    boost kernel into ``stat_max``) -> per level {hist_build, hist_reduce,
-    [RCCL all-reduce], split_find, level_finalize, partition} -> exact leaf
-    sums (leaf_stats, [all-reduce], leaf_finalize).
-    """
+
+def hist_mode(pkm: int, copies: int = 1, nid16: bool = False, batch: bool = False) -> int:
+    return pkm + HIST_COPIES.get(copies, 0) + (HIST_NID16 if nid16 else 0) + (HIST_BATCH_LOOP if batch else 0)
+
+
+class HipTreeBuilder:
+    """Builds one tree per call entirely with enqueued HIP kernels."""
 
     # LDS histogram bytes per workgroup / threads per workgroup / target grid
     # (the sweeps that fixed them: profiles/r3/hist_threads_ab.txt,
@@ -91,12 +99,6 @@ class HipTreeBuilder:
     # resolution is 2^30 / (largest chunk) levels (see tree_begin)
     ROWS_CAP = 262144
     SYNC_NODE_CAP = 4096   # above this many potential nodes the host reads the real count
-    # (Removed A/B variants that measured slower and no longer exist: the
-    # wave-compacted column gather (profiles/compact_hist_p9.txt), the
-    # row-major built-row gather (profiles/r3/hist_rm_ab.txt), the route_kernel
-    # routing pass, split_find_fin / split_level fused splits
-    # (profiles/r3/hist_threads_ab.txt) and the segment-ordered code-row moves
-    # (profiles/r4/drf/move_rows_ab.txt).)
     SEG_TARGET_CHUNKS = 1024   # level-0 histogram chunks (2 resident 57 KB workgroups per CU)
     # segmented-histogram LDS per workgroup (feature group size): small histograms (<= 64 bins)
     # run more, narrower groups - DRF 10M x 100 depth 20: 64 / 32 / 24 / 16 / 12 / 8 / 4 KB ->
@@ -706,8 +708,6 @@ class HipTreeBuilder:
                                                     P(ctl_cur), P(built), st), "hist_reduce")
             hist_elems = plan["slot_cnt"] * plan["fg"] * nbt
             partials = self._buf("partials", plan["n_groups"] * plan["wgpg"] * hist_elems, torch.int64)
-            # level 0 streams every row; deeper levels touch only the built
-            # (smaller) children -> wave-compacted kernel keeps atomics dense
             for ps in range(plan["passes"]):
                 slot_lo = ps * plan["slot_cnt"]
                 with T("hist"):
@@ -718,7 +718,7 @@ class HipTreeBuilder:
                             P(part_prev), P(ctl_nxt), P(nid_buf[d % 2]), P(ctl_cur), P(nvb_h), P(self.qscale),
                             Fh, nbt, plan["fg"], plan["n_groups"], plan["wgpg"], plan["slot_cnt"],
                             self.ROWS_PER_LANE, plan["threads"], P(self.pk),
-                            (4 if self.pk32 else 2) + (64 if nid16 else 0), P(partials), *pend["args"],
+                            hist_mode(4 if self.pk32 else 2, nid16=nid16), P(partials), *pend["args"],
                             P(joint), P(plane_src), st),
                             "hist_build_route_fin")
                         pend = None
@@ -730,7 +730,7 @@ class HipTreeBuilder:
                             P(nid_buf[d % 2]), 1 if ps == 0 else 0, P(ctl_cur), P(nvb_h), P(self.qscale), Fh, nbt,
                             plan["fg"], plan["n_groups"], plan["wgpg"], slot_lo, plan["slot_cnt"],
                             self.ROWS_PER_LANE, plan["threads"], P(self.pk),
-                            (4 if self.pk32 else 2) + (64 if nid16 else 0),
+                            hist_mode(4 if self.pk32 else 2, nid16=nid16),
                             P(partials), P(joint), P(plane_src), st),
                             "hist_build_route")
                     elif d == 0 and grad_fuse is not None:
@@ -753,10 +753,9 @@ class HipTreeBuilder:
                             P(self.qscale), tree_index & 0x7FFFFFFF, Fh, nbt, plan["fg"], plan["n_groups"],
                             plan["wgpg"], slot_lo, plan["slot_cnt"], self.ROWS_PER_LANE, plan["threads"],
                             P(self.slot16), P(self.pk),
-                            ((6 if pk_boost else 1 + (2 if self.pk32 else 0)) if d == 0
-                             else 2 + (2 if self.pk32 else 0))
-                            + ({8: 16, 4: 32}.get(self.L0_COPIES, 0) if l0_copies else 0)
-                            + (128 if batch else 0),
+                            hist_mode((6 if pk_boost else 3 if self.pk32 else 1) if d == 0
+                                      else (4 if self.pk32 else 2),
+                                      copies=self.L0_COPIES if l0_copies else 1, batch=batch),
                             P(partials), P(joint), P(plane_src), st),
                             "hist_build")
                 with T("hist_reduce"):

@@ -39,10 +39,8 @@ TREE_SIGS = {
     "h2omx_hist_build_route_fin": "PLPPPPPPPIIIIIIIIPIPPPPIPPS",
     "h2omx_partition_route_fin": "PLPPPIPPIPIPPPIS",
     "h2omx_partition_final_fin": "PLPPPIPPPPIPPPIPPPIPPPPIS",
-    "h2omx_leaf_reduce": "PIIPS",
     "h2omx_boost_update": "PPPLLPPPPPPPLPIPIPPIIPPS",
     "h2omx_apply_tree": "PLPPS",
-    "h2omx_tree_archive": "PLPIPS",
     "h2omx_sketch_bins": "",
     "h2omx_sketch": "PLIIIPIPPPPPPPPPPPPS",
     "h2omx_softmax_grad": "PILPPLLIPPPPPPS",
@@ -50,7 +48,6 @@ TREE_SIGS = {
     "h2omx_stat_blocks": "",
     "h2omx_stat_reduce": "PPS",
     "h2omx_tree_begin": "PIIPPPPILIPS",
-    "h2omx_leaf_stats": "PPPPLPIPS",
     "h2omx_leaf_finalize": "PPPPPIS",
     "h2omx_leaf_finalize_begin": "PPPPPIPIIPPLPS",
     "h2omx_leaf_finalize_mono": "PPPPPIPS",

@@ -466,6 +466,51 @@ def test_seg_colmajor_transpose(cuda_dev, F, fp):
     assert torch.equal(got, want)
 
 
+def test_hist_build_rejects_removed_variants(cuda_dev):
+    """The histogram launcher takes 16-row units only, no mode bit 3 (the
+    wave-compacted variant is gone) and routed levels with int16 node ids only
+    (mode bit 6): anything else is the bad-argument status, and nothing is
+    launched - the slabs keep their sentinel.  Every buffer is valid for the
+    kernel each call would have selected."""
+    from h2omx import ops
+
+    lib, P, st = ops.tree_lib(), ops.P, ops.stream(cuda_dev)
+    BAD_ARG = 1   # csrc/common.h kBadArg
+    npad, F, nbt, fg, n_groups, wgpg, slot_cnt, threads = 1024, 2, 32, 2, 1, 8, 1, 64
+    gen = torch.Generator().manual_seed(5)
+    i32 = dict(dtype=torch.int32, device=cuda_dev)
+    codes = torch.randint(0, 20, (F * npad,), generator=gen, dtype=torch.uint8).to(cuda_dev)
+    g = torch.randn((npad,), generator=gen).to(cuda_dev)
+    s2 = torch.rand((npad,), generator=gen).to(cuda_dev)
+    nid = torch.zeros((npad,), **i32)                       # every row in node 0
+    nid_out = torch.full((npad,), -1, **i32)
+    link = torch.tensor([0, -1, -1, 0], **i32)              # NodeLink of node 0: built in slot 0
+    ctl = torch.tensor([1, 1, 0, 1], **i32)                 # one node, one slot
+    part = torch.tensor([0, 10, 0, 0, 0, 0, 1, 1 << 16], **i32)   # PartInfo: node 0 splits on feature 0, slots 0 | 1
+    nvb = torch.tensor([20, 20], **i32)
+    qscale = torch.zeros((16,), dtype=torch.float64, device=cuda_dev)
+    qscale[0], qscale[1], qscale[8] = 1024.0, 1024.0, float(npad)
+    slot16 = torch.zeros((npad,), dtype=torch.int16, device=cuda_dev)
+    pk = torch.zeros((npad,), dtype=torch.int64, device=cuda_dev)
+    sentinel = 0x5A5A5A5A5A5A5A5A
+    partials = torch.full((n_groups * wgpg * slot_cnt * fg * nbt,), sentinel, dtype=torch.int64, device=cuda_dev)
+
+    def hist_build(rows_per_lane, mode):
+        return lib.h2omx_hist_build(P(codes), npad, P(g), P(s2), P(nid), P(link), P(ctl), P(nvb), P(qscale), 0, F, nbt,
+                                    fg, n_groups, wgpg, 0, slot_cnt, rows_per_lane, threads, P(slot16), P(pk), mode,
+                                    P(partials), None, None, st)
+
+    assert hist_build(8, 0) == BAD_ARG                      # (a) 8-row units
+    assert hist_build(16, 2 | 8) == BAD_ARG                 # (b) mode bit 3
+    rc = lib.h2omx_hist_build_route(P(codes), npad, P(nid), P(part), P(ctl), P(nid_out), 1, P(ctl), P(nvb), P(qscale),
+                                    F, nbt, fg, n_groups, wgpg, 0, slot_cnt, 16, threads, P(pk), 4, P(partials),
+                                    None, None, st)
+    assert rc == BAD_ARG                                    # (c) routed level without int16 node ids (bit 6)
+    torch.cuda.synchronize(cuda_dev)
+    assert bool((partials == sentinel).all())
+    assert bool((nid_out == -1).all())
+
+
 def test_mean_leaves_without_h_match(cuda_dev, monkeypatch):
     """DRF (mean leaves) on the segmented engine: partitions given no h (their
     H sums are unused) grow the same trees, values and weights."""
