@@ -749,3 +749,221 @@ H2OMX_API int h2omx_contrib_rank(const float* phi, int64_t ld, int64_t n, int F,
 #undef LAUNCH_RANK
   return launch_status();
 }
+
+// ---------------------------------------------------------------------------
+// DeepSHAP (DeepLIFT rescale rule) for the Deep Learning MLP
+// ---------------------------------------------------------------------------
+// A pair (scored row x, background row b) back-propagates multipliers through
+// the net: with the hidden pre-activations a = zx[h], b = zb[h] of a layer and
+// the multipliers G of its outputs, U = G * r(a, b) and the layer below gets
+// G' = U W (the project's GEMM).  r is the secant slope (f(a) - f(b)) / (a - b)
+// of the activation f, written so that nothing cancels (d = a - b):
+//   Rectifier     1 if a, b > 0;  0 if a, b <= 0;  a / (a - b) if a > 0 >= b;
+//                 b / (b - a) if b > 0 >= a (a tie lands in the first two).
+//   Tanh          s(d) (1 - tanh a tanh b), s(d) = tanh(d) / d, s(0) = 1
+//                 (tanh a - tanh b = tanh(a - b) (1 - tanh a tanh b)); at a tie
+//                 this is the derivative 1 - tanh^2 a.
+//   ExpRectifier  (ELU, alpha = 1)  1 if a, b > 0;
+//                 e^max(a,b) (-expm1(-|d|)) / |d| if a, b <= 0, e^a at d = 0:
+//                 the same number as e^min(a,b) expm1(|d|) / |d| with every
+//                 factor in [0, 1], so a wide gap cannot give 0 * inf;
+//                 (a - expm1(b)) / (a - b) if a > 0 >= b (both terms of the
+//                 numerator are >= 0), mirrored for b > 0 >= a.
+// Every branch is a quotient of same-signed finite terms or a product of
+// bounded ones: no epsilon, and finite inputs give a finite r in [0, 1].
+//
+// deepshap_rescale_kernel is a pure stream over the [pairs][h] planes (pair =
+// i * nb + j, x-major).  Lanes run along the unit axis, so a wave moves 256
+// contiguous bytes of a row of G, U, Zx and Zb per instruction.  A workgroup
+// (4 waves) owns 64 units of one scored row: every lane keeps its zx (and what
+// depends on zx alone) in registers while wave w walks the background rows
+// w, w + 4 gridDim.z, ... of the workgroup's share; Zb [nb][h] is re-read by
+// every scored row and stays in L2.  For the top hidden layer G is the vector
+// g_L [h] (VEC), held in a register as well, never a [pairs][h] plane.  U may
+// be G: an element is read and written by the same lane.
+namespace {
+
+constexpr int kDsWaves = 4;  // waves (background rows in flight) per workgroup
+
+template <int ACT>
+struct DsRow;  // what depends on the scored row's pre-activation alone
+
+template <>
+struct DsRow<1> {
+  float a;
+  __device__ explicit DsRow(float a_) : a(a_) {}
+  __device__ float r(float b) const {
+    const bool pa = a > 0.0f, pb = b > 0.0f;
+    if (pa == pb) return pa ? 1.0f : 0.0f;
+    return pa ? a / (a - b) : b / (b - a);
+  }
+};
+
+template <>
+struct DsRow<2> {
+  float a, ta;
+  __device__ explicit DsRow(float a_) : a(a_), ta(tanhf(a_)) {}
+  __device__ float r(float b) const {
+    const float d = a - b;
+    const float s = d == 0.0f ? 1.0f : tanhf(d) / d;
+    return s * (1.0f - ta * tanhf(b));
+  }
+};
+
+template <>
+struct DsRow<4> {
+  float a, ea, ema;  // e^a and expm1(a), used where a <= 0
+  __device__ explicit DsRow(float a_) : a(a_), ea(expf(fminf(a_, 0.0f))), ema(expm1f(fminf(a_, 0.0f))) {}
+  __device__ float r(float b) const {
+    const bool pa = a > 0.0f, pb = b > 0.0f;
+    if (pa && pb) return 1.0f;
+    if (pa) return (a - expm1f(b)) / (a - b);
+    if (pb) return (b - ema) / (b - a);
+    const float ad = fabsf(a - b);
+    const float top = a >= b ? ea : expf(b);
+    return ad == 0.0f ? ea : top * (-expm1f(-ad)) / ad;
+  }
+};
+
+template <int ACT, bool VEC>
+__global__ __launch_bounds__(kDsWaves * kWave) void deepshap_rescale_kernel(const float* G,
+                                                                           const float* __restrict__ Zx,
+                                                                           const float* __restrict__ Zb, float* U,
+                                                                           int nb, int h) {
+  const int lane = threadIdx.x & (kWave - 1);
+  const int wave = threadIdx.x / kWave;
+  const int c = blockIdx.y * kWave + lane;
+  if (c >= h) return;
+  const int64_t i = blockIdx.x;
+  const DsRow<ACT> row(Zx[i * h + c]);
+  const float gv = VEC ? G[c] : 0.0f;
+  const int step = kDsWaves * (int)gridDim.z;
+  const int64_t base = i * nb;
+  int j = (int)blockIdx.z * kDsWaves + wave;
+  // two background rows per trip: their loads are independent
+  for (; j + step < nb; j += 2 * step) {
+    const int64_t o0 = (base + j) * h + c, o1 = (base + j + step) * h + c;
+    const float b0 = Zb[(int64_t)j * h + c], b1 = Zb[(int64_t)(j + step) * h + c];
+    const float g0 = VEC ? gv : G[o0], g1 = VEC ? gv : G[o1];
+    U[o0] = g0 * row.r(b0);
+    U[o1] = g1 * row.r(b1);
+  }
+  if (j < nb) {
+    const int64_t o0 = (base + j) * h + c;
+    U[o0] = (VEC ? gv : G[o0]) * row.r(Zb[(int64_t)j * h + c]);
+  }
+}
+
+// deepshap_fold_kernel: G0 [rows * nb][p] holds a pair's multipliers of the p
+// design columns.  Design column f contributes scale G0[pair][f] (xs[i][f] -
+// bs[j][f]); predictor c owns the columns col_start[c] .. col_start[c + 1] - 1,
+// added in that order.  MEAN = false writes the pair's value to out[c][pair],
+// MEAN = true the mean over the background to out[c][i]: one thread adds the
+// pairs j = 0 .. nb - 1 of its (i, c) in index order and divides once, so the
+// result does not depend on a schedule and is bit-identical between calls (no
+// atomics).  Threads take (row, c) with c fastest, so a wave reads whole rows
+// of G0; the tile is turned in LDS ([c][row], padded) and written with lanes
+// along the row axis of the feature-major output.
+constexpr int kFoldC = 64;  // predictors per LDS tile
+// output rows per workgroup: pairs, or (MEAN) scored rows, few of them because each is a walk over nb pairs
+constexpr int kFoldPairs = 64, kFoldMeanRows = 8;
+
+template <bool MEAN>
+__global__ __launch_bounds__(256) void deepshap_fold_kernel(const float* __restrict__ G0, const float* __restrict__ xs,
+                                                            const float* __restrict__ bs,
+                                                            const int* __restrict__ col_start, float scale,
+                                                            int64_t rows, int nb, int p, int C, int64_t ldo,
+                                                            float* __restrict__ out) {
+  constexpr int TR = MEAN ? kFoldMeanRows : kFoldPairs;
+  __shared__ float tile[kFoldC * (TR + 1)];
+  const int tid = threadIdx.x;
+  const int64_t r0 = (int64_t)blockIdx.x * TR;
+  const int nr = (int)(rows - r0 < TR ? rows - r0 : TR);
+  for (int c0 = 0; c0 < C; c0 += kFoldC) {
+    const int cc = C - c0 < kFoldC ? C - c0 : kFoldC;
+    for (int t = tid; t < nr * cc; t += 256) {
+      const int rl = t / cc, cl = t - rl * cc;
+      const int f0 = col_start[c0 + cl], f1 = col_start[c0 + cl + 1];
+      const int64_t r = r0 + rl;
+      float v;
+      if (MEAN) {
+        const float* __restrict__ x = xs + r * p;
+        float acc = 0.0f;
+#pragma unroll 4
+        for (int j = 0; j < nb; ++j) {
+          const float* __restrict__ g = G0 + (r * nb + j) * p;
+          const float* __restrict__ b = bs + (int64_t)j * p;
+          float s = 0.0f;
+          for (int f = f0; f < f1; ++f) s += scale * g[f] * (x[f] - b[f]);
+          acc += s;
+        }
+        v = acc / (float)nb;
+      } else {
+        const int64_t i = r / nb;
+        const float* __restrict__ x = xs + i * p;
+        const float* __restrict__ b = bs + (r - i * nb) * p;
+        const float* __restrict__ g = G0 + r * p;
+        v = 0.0f;
+        for (int f = f0; f < f1; ++f) v += scale * g[f] * (x[f] - b[f]);
+      }
+      tile[cl * (TR + 1) + rl] = v;
+    }
+    __syncthreads();
+    for (int t = tid; t < cc * TR; t += 256) {
+      const int cl = t / TR, rl = t - cl * TR;
+      if (rl < nr) out[(int64_t)(c0 + cl) * ldo + r0 + rl] = tile[cl * (TR + 1) + rl];
+    }
+    __syncthreads();
+  }
+}
+
+}  // namespace
+
+// U[(i nb + j)][c] = G[..] r(Zx[i][c], Zb[j][c]) over ni scored rows, nb
+// background rows and h units; act = 1 Rectifier, 2 Tanh, 4 ExpRectifier.
+// g_is_vector: G is the [h] vector every pair shares (top hidden layer), else
+// the [ni nb][h] plane, which U may alias.
+H2OMX_API int h2omx_deepshap_rescale(const float* G, int g_is_vector, const float* Zx, const float* Zb, float* U,
+                                     int64_t ni, int nb, int h, int act, hipStream_t stream) {
+  if (ni <= 0 || nb <= 0 || h <= 0 || (act != 1 && act != 2 && act != 4)) return kBadArg;
+  const int64_t gy = (h + kWave - 1) / kWave;
+  if (ni > 0x7FFFFFFF || gy > 65535) return kBadArg;
+  // enough workgroups for a small block of scored rows, at most one wave per background row
+  int64_t gz = 2048 / (ni * gy);
+  const int64_t zmax = (nb + kDsWaves - 1) / kDsWaves;
+  gz = gz < 1 ? 1 : (gz > zmax ? zmax : gz);
+  if (gz > 65535) gz = 65535;
+  const dim3 grid((unsigned)ni, (unsigned)gy, (unsigned)gz), blk(kDsWaves * kWave);
+#define LAUNCH_DS(A)                                                                                             \
+  if (g_is_vector)                                                                                               \
+    hipLaunchKernelGGL((deepshap_rescale_kernel<A, true>), grid, blk, 0, stream, G, Zx, Zb, U, nb, h);           \
+  else                                                                                                           \
+    hipLaunchKernelGGL((deepshap_rescale_kernel<A, false>), grid, blk, 0, stream, G, Zx, Zb, U, nb, h)
+  if (act == 1) { LAUNCH_DS(1); }
+  else if (act == 2) { LAUNCH_DS(2); }
+  else { LAUNCH_DS(4); }
+#undef LAUNCH_DS
+  return launch_status();
+}
+
+// G0 [ni nb][p], xs [ni][p], bs [nb][p], col_start [C + 1] (ascending, 0 .. p).
+// mean = 0: out[c][ldo] gets the ni nb pairs (x-major) from column 0 on;
+// mean = 1: it gets the ni background means.  The caller offsets ``out`` to
+// the block's first row; ldo is the row length of the whole result.
+H2OMX_API int h2omx_deepshap_fold(const float* G0, const float* xs, const float* bs, const int* col_start, float scale,
+                                  int64_t ni, int nb, int p, int C, int mean, int64_t ldo, float* out,
+                                  hipStream_t stream) {
+  if (ni <= 0 || nb <= 0 || p <= 0 || C <= 0) return kBadArg;
+  const int64_t rows = mean ? ni : ni * nb;
+  if (ldo < rows) return kBadArg;
+  const int tr = mean ? kFoldMeanRows : kFoldPairs;
+  const int64_t gx = (rows + tr - 1) / tr;
+  if (gx > 0x7FFFFFFF) return kBadArg;
+  if (mean)
+    hipLaunchKernelGGL((deepshap_fold_kernel<true>), dim3((unsigned)gx), dim3(256), 0, stream, G0, xs, bs, col_start,
+                       scale, rows, nb, p, C, ldo, out);
+  else
+    hipLaunchKernelGGL((deepshap_fold_kernel<false>), dim3((unsigned)gx), dim3(256), 0, stream, G0, xs, bs, col_start,
+                       scale, rows, nb, p, C, ldo, out);
+  return launch_status();
+}

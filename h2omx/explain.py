@@ -13,7 +13,10 @@ or, with ``output_per_reference=True``, one row per (row, background row).
 ``top_n=`` / ``bottom_n=`` / ``compare_abs=`` return, for any of these forms,
 each row's strongest features by name and value instead of every column; on
 the device contrib_rank_kernel ranks the contribution planes where the SHAP
-kernels left them.
+kernels left them.  For a Deep Learning model ``background_frame=`` gives
+DeepSHAP (DeepLIFT's rescale rule per pair) in the same forms: on the device
+deepshap_rescale_kernel and deepshap_fold_kernel around the project's GEMM,
+on CPU frames the same closed forms in float64.
 
 ``friedman_h(model, frame, variables)`` (H2O ``model.h``): Friedman and
 Popescu's H statistic of 2 or more numerical variables, from the partial
@@ -435,6 +438,222 @@ def _contributions_background(model, ens, X, Bm, lv, el, maxm, sets, per_referen
     return Frame(vecs)
 
 
+# ---------------------------------------------------------------------------
+# DeepSHAP (Deep Learning models)
+# ---------------------------------------------------------------------------
+# pairs per block on the device: one GEMM launch takes 65535 row tiles of at least 64 rows
+_DEEPSHAP_MAX_PAIRS = 65535 * 64
+_DEEPSHAP_CPU_BLOCK = 1 << 24        # float64 elements of one [rows][nb][width] temporary on the CPU
+
+
+def _deepshap_multiplier(act: int, a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
+    """The rescale rule's multiplier r(a, b) = (f(a) - f(b)) / (a - b) of the
+    activation ``act`` (1 Rectifier, 2 Tanh, 4 ExpRectifier) in the
+    cancellation-free closed forms of csrc/explain_kernels.hip
+    (deepshap_rescale_kernel), on broadcastable float64 tensors."""
+    d = a - b
+    one = torch.ones_like(d)
+    if act == 2:
+        nz = d != 0
+        s = torch.where(nz, torch.tanh(d) / torch.where(nz, d, one), one)
+        return s * (1.0 - torch.tanh(a) * torch.tanh(b))
+    pa, pb = (a > 0).expand_as(d), (b > 0).expand_as(d)
+    mixed = pa != pb
+    den = torch.where(mixed, d, one).abs()                      # a - b or b - a, whichever is positive
+    if act == 1:
+        return torch.where(mixed, torch.where(pa, a, b) / den, (pa & pb).to(d.dtype))
+    if act != 4:
+        raise ValueError(f"no DeepSHAP multiplier for activation code {act}")
+    a0, b0 = a.clamp(max=0.0), b.clamp(max=0.0)                 # the branches that read them have a, b <= 0
+    up = torch.where(pa, a - torch.expm1(b0), b - torch.expm1(a0)) / den
+    ad = d.abs()
+    low = torch.where(ad == 0, torch.exp(a0),
+                      torch.exp(torch.maximum(a0, b0)) * -torch.expm1(-ad) / torch.where(ad == 0, one, ad))
+    return torch.where(mixed, up, torch.where(pa, one, low))
+
+
+def _deepshap_pre64(act: int, Ws, biases, X: torch.Tensor) -> list:
+    """float64 pre-activations [Z_1, ..., Z_L, Z_out] of the design rows X."""
+    f = {1: torch.relu, 2: torch.tanh, 4: torch.nn.functional.elu}[act]
+    Zs = []
+    for W, b in zip(Ws, biases):
+        Zs.append((f(Zs[-1]) if Zs else X.double()) @ W.T + b)
+    return Zs
+
+
+def _deepshap_host(act: int, Ws, w_out, xs: torch.Tensor, bs: torch.Tensor, Zx, Zb, scale: float, col_start,
+                   per_reference: bool) -> torch.Tensor:
+    """DeepSHAP in float64 on the CPU, block by block of scored rows: [C][n * nb]
+    x-major pairs or the [C][n] mean over the background of the design rows xs
+    [n][p] against bs [nb][p].  ``Ws`` are the hidden layers' weights, ``w_out``
+    [h_L] the output row, ``Zx`` / ``Zb`` the hidden pre-activations."""
+    n, p = xs.shape
+    nb = int(bs.shape[0])
+    C = len(col_start) - 1
+    xs, bs = xs.double(), bs.double()
+    out = torch.zeros((C, n * nb if per_reference else n), dtype=torch.float64)
+    width = max([p] + [int(W.shape[0]) for W in Ws])
+    step = max(1, _DEEPSHAP_CPU_BLOCK // max(1, nb * width))
+    for i0 in range(0, n, step):
+        i1 = min(n, i0 + step)
+        G = w_out.expand(i1 - i0, nb, -1)
+        for l in range(len(Ws) - 1, -1, -1):
+            U = G * _deepshap_multiplier(act, Zx[l][i0:i1, None, :], Zb[l][None, :, :])
+            G = U @ Ws[l]
+        phi = scale * G * (xs[i0:i1, None, :] - bs[None, :, :])                        # [rows][nb][p]
+        fold = torch.stack([phi[..., col_start[c]: col_start[c + 1]].sum(-1) for c in range(C)])
+        if per_reference:
+            out[:, i0 * nb: i1 * nb] = fold.reshape(C, -1)
+        else:
+            out[:, i0:i1] = fold.sum(2) / nb
+    return out
+
+
+def _deepshap_rows(nb: int, width: int, budget: int) -> int:
+    """Scored rows per block of the device path: the two [rows * nb][width]
+    float32 work buffers within ``budget`` bytes and one GEMM launch."""
+    one = 2 * 4 * nb * width
+    rows = min(int(budget) // one, _DEEPSHAP_MAX_PAIRS // nb, (2 ** 31 - 1) // (nb * width))
+    if rows < 1:
+        raise ValueError(f"predict_contributions of one row against {nb} background rows needs {one} bytes of work "
+                         f"space; the limit is {int(budget)} bytes and {_DEEPSHAP_MAX_PAIRS} pairs per block: use "
+                         "fewer background rows")
+    return rows
+
+
+def _deepshap_device(act: int, Ws, w_out: torch.Tensor, xs: torch.Tensor, bs: torch.Tensor, Zx, Zb, scale: float,
+                     col_start, per_reference: bool, *, _budget: int | None = None) -> torch.Tensor:
+    """The HIP path (csrc/explain_kernels.hip deepshap_rescale_kernel,
+    deepshap_fold_kernel and the project's GEMM between them): float32
+    [C][n * nb] x-major pairs or the [C][n] background mean.  ``Zx`` / ``Zb``
+    are the hidden pre-activations of xs [n][p] / bs [nb][p].  Scored rows go
+    in blocks whose two work buffers fit ``_budget`` bytes (half of the free
+    device memory by default)."""
+    from .ops import P, check, explain_lib, stream
+    from .ops import dense as OD
+
+    n, p = (int(a) for a in xs.shape)
+    nb = int(bs.shape[0])
+    C = len(col_start) - 1
+    dev = xs.device
+    L = len(Ws)
+    width = max([p] + [int(W.shape[0]) for W in Ws])
+    if _budget is None:
+        _budget = torch.cuda.mem_get_info(dev)[0] // 2
+    rows = min(_deepshap_rows(nb, width, _budget), max(n, 1))
+    out = torch.empty((C, n * nb if per_reference else n), dtype=torch.float32, device=dev)
+    ldo = int(out.shape[1])
+    if n == 0:
+        return out
+    bufs = [torch.empty((rows * nb * width,), dtype=torch.float32, device=dev) for _ in range(2 if L else 1)]
+    cs = torch.tensor(list(col_start), dtype=torch.int32, device=dev)
+    lib, st = explain_lib(), stream(dev)
+    xs, bs = xs.float().contiguous(), bs.float().contiguous()
+    Ws = [W.float().contiguous() for W in Ws]
+    Zx = [Z.float().contiguous() for Z in Zx]
+    Zb = [Z.float().contiguous() for Z in Zb]
+    w_out = w_out.float().contiguous()
+    for i0 in range(0, n, rows):
+        ni = min(rows, n - i0)
+        pairs = ni * nb
+        cur = 0
+        if L == 0:
+            bufs[0][: pairs * p].view(pairs, p).copy_(w_out.expand(pairs, p))
+        for l in range(L - 1, -1, -1):
+            h = int(Ws[l].shape[0])
+            U = bufs[cur][: pairs * h].view(pairs, h)
+            # the top layer's multipliers are the output row itself, passed as a vector
+            check(lib.h2omx_deepshap_rescale(P(w_out if l == L - 1 else U), int(l == L - 1), P(Zx[l][i0: i0 + ni]),
+                                             P(Zb[l]), P(U), ni, nb, h, act, st), "deepshap_rescale")
+            k = int(Ws[l].shape[1])
+            OD.gemm(U, Ws[l], out=bufs[1 - cur][: pairs * k].view(pairs, k))
+            cur = 1 - cur
+        dst = out[:, i0 * nb if per_reference else i0:]
+        check(lib.h2omx_deepshap_fold(P(bufs[cur]), P(xs[i0: i0 + ni]), P(bs), P(cs), float(scale), ni, nb, p, C,
+                                      int(not per_reference), ldo, P(dst), st), "deepshap_fold")
+    return out
+
+
+def _contributions_deeplearning(model, frame: Frame, background_frame: Frame | None, per_reference: bool, top_n,
+                                bottom_n, compare_abs: bool, *, _budget: int | None = None) -> Frame:
+    """DeepSHAP (DeepLIFT's rescale rule) of a Deep Learning model against the
+    rows of ``background_frame``: docs/ALGORITHMS.md, "Explanations"."""
+    if model.autoencoder:
+        raise ValueError("predict_contributions does not support autoencoders: there is no single output to explain")
+    if model.category not in (ModelCategory.REGRESSION, ModelCategory.BINOMIAL):
+        raise ValueError("predict_contributions supports regression and binomial Deep Learning models, not "
+                         f"multinomial ones ({len(model.response_domain or [])} classes)")
+    if model.act == 3:
+        raise ValueError("predict_contributions does not support the Maxout activation: the rescale rule needs an "
+                         "elementwise activation")
+    if model.params.get("offset_column"):
+        raise ValueError("predict_contributions does not support Deep Learning models fitted with an offset_column")
+    if background_frame is None:
+        raise ValueError("predict_contributions of a Deep Learning model needs a background_frame: DeepSHAP "
+                         "explains a row against reference rows")
+    design = model.design
+    cols, col_start = [], [0]
+    for c in design.x:
+        k = sum(1 for col, _ in design.spec if col == c)
+        if k:
+            cols.append(c)
+            col_start.append(col_start[-1] + k)
+    # a predictor's design columns are adjacent (DesignInfo.spec), so a column range per predictor is enough
+    owner = [c for j, c in enumerate(cols) for _ in range(col_start[j], col_start[j + 1])]
+    assert owner == [col for col, _ in design.spec]
+    C = len(cols)
+    kt, kb = _rank_spec(top_n, bottom_n, C)
+    xs = model._rows(model.adapt_frame(frame))                                        # [n][p]
+    bs = model._rows(model.adapt_frame(background_frame)).to(xs.device)
+    n, p = (int(a) for a in xs.shape)
+    nb = int(bs.shape[0])
+    if nb == 0:
+        raise ValueError("background_frame has no rows")
+    dev = xs.device
+    result = 4 * n * (nb * (C + 3) if per_reference else C + 1)
+    if per_reference:
+        result += 8 * (kt + kb) * n * nb
+    limit = torch.cuda.mem_get_info(dev)[0] // 2 if xs.is_cuda else _CPU_CONTRIB_LIMIT
+    if result > limit:
+        raise ValueError(f"predict_contributions of {n} rows against {nb} background rows needs {result} bytes for "
+                         f"the result; the limit is {limit} bytes: use fewer background rows or score the frame in "
+                         "parts")
+    net = model.net
+    L = len(net.layers) - 1
+    binomial = model.category == ModelCategory.BINOMIAL
+    scale = 1.0 if binomial else float(model.y_sd)
+    Wo = net.W(L).to(dev)
+    w_out = (Wo[1] - Wo[0]) if binomial else Wo[0]
+    Ws = [net.W(i).to(dev) for i in range(L)]
+    if xs.is_cuda:
+        Zx, Zb = model.preactivations(xs), model.preactivations(bs)
+        zb = Zb[-1]
+        out = _deepshap_device(model.act, Ws, w_out, xs, bs, Zx[:-1], Zb[:-1], scale, col_start, per_reference,
+                               _budget=_budget)
+    else:
+        Wd = [net.W(i).double() for i in range(L + 1)]
+        bd = [net.b(i).double() for i in range(L + 1)]
+        Zx, Zb = _deepshap_pre64(model.act, Wd, bd, xs), _deepshap_pre64(model.act, Wd, bd, bs)
+        zb = Zb[-1]
+        out = _deepshap_host(model.act, Wd[:L], w_out.double(), xs, bs, Zx[:-1], Zb[:-1], scale, col_start,
+                             per_reference).float()
+    margin_b = ((zb[:, 1] - zb[:, 0]) if binomial else zb[:, 0] * model.y_sd + model.y_mean).float()
+    vecs = []
+    if per_reference:
+        rows = torch.arange(n, dtype=torch.float32, device=dev)
+        refs = torch.arange(nb, dtype=torch.float32, device=dev)
+        vecs += [Vec("RowIdx", rows.repeat_interleave(nb), INT), Vec("BackgroundRowIdx", refs.repeat(n), INT)]
+        bias = margin_b.repeat(n)
+    else:
+        bias = torch.full((n,), float(margin_b.double().mean()), dtype=torch.float32, device=dev)
+    if kt + kb:
+        idx, val = _rank(out, kt, kb, compare_abs)
+        return _ranked_frame(cols, idx, val, vecs, Vec("BiasTerm", bias, "real"), kt=kt)
+    vecs += [Vec(c, out[j], "real") for j, c in enumerate(cols)]
+    vecs.append(Vec("BiasTerm", bias, "real"))
+    return Frame(vecs)
+
+
 def predict_contributions(model, frame: Frame, *, background_frame: Frame | None = None,
                           output_per_reference: bool = False, top_n=None, bottom_n=None, compare_abs: bool = False,
                           output_format: str = "Original") -> Frame:
@@ -451,8 +670,14 @@ def predict_contributions(model, frame: Frame, *, background_frame: Frame | None
     order as ``top_feature_i`` / ``top_value_i`` and ``bottom_feature_i`` /
     ``bottom_value_i`` (see :func:`_rank_spec`); ``compare_abs`` orders by
     magnitude, the values keep their sign.  Ties go to the lower column index
-    in both orders."""
+    in both orders.
+
+    A Deep Learning model needs ``background_frame`` and is explained by
+    DeepSHAP (:func:`_contributions_deeplearning`), in the same forms."""
     _output_format(output_format)
+    if model.algo == "deeplearning":
+        return _contributions_deeplearning(model, frame, background_frame, bool(output_per_reference), top_n, bottom_n,
+                                           bool(compare_abs))
     ens = getattr(model, "ens", None)
     if ens is None or model.algo not in ("gbm", "drf", "xgboost", "generic"):
         raise NotImplementedError(f"predict_contributions is available for tree models, not {model.algo}")

@@ -587,6 +587,18 @@ class DeepLearningModel(Model):
             outs.append(Hs[-1])
         return torch.cat(outs) if outs else torch.zeros((0, self.net.sizes[-1]), device=X.device)
 
+    def preactivations(self, X) -> list:
+        """[Z_1, ..., Z_L, Z_out] of the design rows X [rows][p] at scoring: every
+        layer's GEMM without its activation, which is applied afterwards (DeepSHAP
+        reads the hidden pre-activations; h2omx.explain)."""
+        if self.act == 3:
+            raise ValueError("Maxout layers have no elementwise pre-activation")
+        f = {1: torch.relu, 2: torch.tanh, 4: torch.nn.functional.elu}[self.act]
+        Zs = []
+        for i in range(len(self.net.layers)):
+            Zs.append(D.gemm(f(Zs[-1]) if Zs else X, self.net.W(i), bias=self.net.b(i), act=0, tb=True))
+        return Zs
+
     def predict_raw(self, frame: Frame) -> torch.Tensor:
         X = self._rows(frame)
         Z = self._score(X)

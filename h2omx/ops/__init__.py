@@ -131,6 +131,10 @@ EXPLAIN_SIGS = {
     "h2omx_pd_sweep": "PLLIPPIIPIPPIIIPIPPS",
     # phi, ld, n, F, kt, kb, compare_abs, idx_out, val_out
     "h2omx_contrib_rank": "PLLIIIIPPS",
+    # G, g_is_vector, Zx, Zb, U, ni, nb, h, act
+    "h2omx_deepshap_rescale": "PIPPPLIIIS",
+    # G0, xs, bs, col_start, scale, ni, nb, p, C, mean, ldo, out
+    "h2omx_deepshap_fold": "PPPPFLIIIILPS",
 }
 
 P2P_SIGS = {
