@@ -27,6 +27,7 @@ KERNEL_LIBS = {
     "explain": ["explain_kernels.hip"],
     "p2p": ["p2p_kernels.hip"],
     "mlp": ["mlp_kernels.hip"],
+    "survival": ["cox_kernels.hip"],
 }
 HOST_LIBS = {
     "host": ["host/parser.cpp", "host/solvers.cpp"],

@@ -26,6 +26,7 @@ import numpy as np
 import torch
 
 from ..frame.frame import ENUM, Frame, Vec
+from ..ops import survival
 from .base import Model, ModelBuilder, ModelCategory
 from .glm import DesignInfo
 
@@ -104,6 +105,12 @@ def _event_sums(t, start, d, w, eta, X, strata, efron: bool):
 
 def concordance(t, d, lp, chunk: int = 2048) -> float:
     """Harrell's C: over comparable pairs (i event, t_j > t_i), P(lp_i > lp_j); ties count 1/2."""
+    if t.is_cuda:
+        return survival.concordance(t, d, lp)
+    return _concordance_torch(t, d, lp, chunk)
+
+
+def _concordance_torch(t, d, lp, chunk: int = 2048) -> float:
     ev = torch.nonzero(d > 0).flatten()
     conc = torch.zeros((), dtype=torch.float64, device=t.device)
     tot = torch.zeros((), dtype=torch.float64, device=t.device)
@@ -220,12 +227,23 @@ class H2OCoxProportionalHazardsEstimator(ModelBuilder):
         Xc = X - torch.from_numpy(x_mean).to(X.device)[None, :]
         beta = torch.full((p,), float(p_["init"]), dtype=torch.float64, device=X.device)
         efron = ties == "efron"
-        ll0, _, _ = _event_sums(t, start, d, w, torch.zeros(n, dtype=torch.float64, device=X.device), Xc, strata,
-                                efron)
+        if X.is_cuda and 1 <= p <= survival.MAX_P:
+            # gfx950 kernels, O(n p) memory: sort once, every pass is h2omx/csrc/cox_kernels.hip
+            engine = "hip"
+            plan = survival.cox_prepare(t, start, d, w, strata, Xc)
+
+            def newton_pass(b):
+                return survival.cox_newton_pass(plan, b, efron)
+        else:
+            engine = "torch"
+
+            def newton_pass(b):
+                return _event_sums(t, start, d, w, Xc @ b, Xc, strata, efron)
+        ll0, _, _ = newton_pass(torch.zeros(p, dtype=torch.float64, device=X.device))
         ll_prev = None
         it = 0
         for it in range(1, int(p_["max_iterations"]) + 1):
-            ll, g, H = _event_sums(t, start, d, w, Xc @ beta, Xc, strata, efron)
+            ll, g, H = newton_pass(beta)
             if ll_prev is not None and float(ll) < float(ll_prev) - 1e-10:
                 # step halving on a decrease (R coxph)
                 beta = 0.5 * (beta + beta_prev)
@@ -239,7 +257,7 @@ class H2OCoxProportionalHazardsEstimator(ModelBuilder):
                     beta = beta_prev
                     break
             ll_prev = ll
-        ll, g, H = _event_sums(t, start, d, w, Xc @ beta, Xc, strata, efron)
+        ll, g, H = newton_pass(beta)
         cov = torch.linalg.inv(-H).cpu().numpy()
         b = beta.cpu().numpy()
         lp = Xc @ beta
@@ -248,5 +266,6 @@ class H2OCoxProportionalHazardsEstimator(ModelBuilder):
                  "wald_test": float(b @ np.linalg.solve(cov, b)) if p else 0.0,
                  "concordance": concordance(t, d, lp), "ties": ties}
         model = CoxPHModel(self, model_id, design, b, cov, x_mean, stats)
+        model.newton_engine = engine
         model.training_metrics = dict(stats)
         return model
