@@ -28,6 +28,11 @@ KERNEL_LIBS = {
     "p2p": ["p2p_kernels.hip"],
     "mlp": ["mlp_kernels.hip"],
     "survival": ["cox_kernels.hip"],
+    "svm": ["svm_kernels.hip"],
+}
+# library name -> extra compiler flags (svm: no packed fp32 instructions)
+KERNEL_FLAGS = {
+    "svm": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
 }
 HOST_LIBS = {
     "host": ["host/parser.cpp", "host/solvers.cpp"],

@@ -15,7 +15,7 @@ import subprocess
 import sys
 from concurrent.futures import ThreadPoolExecutor
 
-from ._native import HOST_LIBS, KERNEL_LIBS, _LIB_DIR, lib_path
+from ._native import HOST_LIBS, KERNEL_FLAGS, KERNEL_LIBS, _LIB_DIR, lib_path
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
@@ -48,7 +48,7 @@ def build_kernel_lib(name: str, force: bool = False, verbose: bool = False) -> s
     if not force and not _stale(out, srcs):
         return out
     cmd = [_hipcc(), f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-shared", "-fPIC",
-           "-munsafe-fp-atomics", "-I", CSRC, "-o", out + ".tmp", *srcs]
+           "-munsafe-fp-atomics", *KERNEL_FLAGS.get(name, []), "-I", CSRC, "-o", out + ".tmp", *srcs]
     if verbose:
         print(" ".join(cmd))
     subprocess.run(cmd, check=True)

@@ -11,12 +11,17 @@ This is a binary kernel SVM trained with the PSVM scheme (Chang et al.,
      * a global arg-max of the residual diagonal (one all-gather);
      * a broadcast of the pivot row and its H row from the owner rank;
      * a kernel column computed locally on every rank.
+   On one rank and a device frame the whole loop runs on the ops.svm kernels
+   with its state on the device (no host round trip per pivot); ties between
+   residual diagonals go to the lowest row index.
 2. A primal-dual interior-point method on the dual
        min 1/2 a^T Q a - 1^T a,  y^T a = 0,  0 <= a_i <= C_i,
    with Q = diag(y) H H^T diag(y) and C_i = hyper_param times the class weight.
    The Newton system (D + Hy Hy^T) is solved with Sherman-Morrison-Woodbury:
    each iteration needs one p x p Gram Hy^T D^-1 Hy, which is all-reduced, and
-   p x p Cholesky solves.  Everything else is row-local vector work plus
+   p x p Cholesky solves.  On a device frame the Gram is ops.svm.wsyrk on the
+   fp64 matrix units and the thin products are ops.svm.tall_tv / tall_v, two
+   right-hand sides per pass over H.  Everything else is row-local vector work plus
    scalar / p-vector all-reduces.  The barrier weight mu shrinks by
    ``mu_factor`` per iteration.  The loop stops when both the surrogate
    duality gap and the primal / dual residuals are below their thresholds.
@@ -34,6 +39,7 @@ import torch
 
 from ..frame.frame import Frame, Vec
 from ..backend import dense as D
+from ..ops import svm as svm_ops
 from .base import Model, ModelBuilder, ModelCategory
 
 
@@ -49,9 +55,29 @@ def _kernel_col(X: torch.Tensor, xsq: torch.Tensor, xp: torch.Tensor, gamma: flo
     return torch.exp(-gamma * d2)
 
 
+def icf_engine(X: torch.Tensor, p: int, comm=None) -> str:
+    """``"hip"`` where icf() runs on the ops.svm kernels: one rank, a device
+    tensor, and a shape within their limits."""
+    n, d = X.shape
+    world = comm.world_size if comm is not None else 1
+    hip = X.is_cuda and world == 1 and n > 0 and 1 <= d <= svm_ops.ICF_MAX_D and 1 <= p <= svm_ops.ICF_MAX_P
+    return "hip" if hip else "torch"
+
+
 def icf(X: torch.Tensor, gamma: float, p: int, thresh: float, comm=None) -> torch.Tensor:
     """Pivoted incomplete Cholesky of the Gaussian kernel over the (sharded)
     rows of X [n][d] fp64 -> H [n][rank] with K ~ H H^T."""
+    if icf_engine(X, p, comm) == "hip":
+        return svm_ops.icf(X, gamma, p, thresh)
+    return _icf_torch(X, gamma, p, thresh, comm)
+
+
+def ipm_engine(H: torch.Tensor) -> str:
+    """``"hip"`` where the interior point takes its products over H from the ops.svm kernels."""
+    return "hip" if H.is_cuda else "torch"
+
+
+def _icf_torch(X: torch.Tensor, gamma: float, p: int, thresh: float, comm=None) -> torch.Tensor:
     n, d = X.shape
     dev = X.device
     world = comm.world_size if comm is not None else 1
@@ -193,8 +219,11 @@ class H2OSupportVectorMachineEstimator(ModelBuilder):
         sv = alpha > thr
         free = sv & (alpha < C - thr)
         # b from the free support vectors (exact kernel values through the low-rank factor)
-        Hy = H * y[:, None]
-        Qa_over_y = H @ (_allsum(Hy.t() @ alpha, comm))            # sum_j a_j y_j K_ij
+        if ipm_engine(H) == "hip":
+            Qa_over_y = svm_ops.tall_v(H, None, _allsum(svm_ops.tall_tv(H, y, alpha[:, None]), comm))[:, 0]
+        else:
+            Hy = H * y[:, None]
+            Qa_over_y = H @ (_allsum(Hy.t() @ alpha, comm))        # sum_j a_j y_j K_ij
         bs = _allsum(torch.stack([(y - Qa_over_y)[free].sum(), free.double().sum()]), comm)
         if float(bs[1]) > 0:
             b = float(bs[0] / bs[1])
@@ -205,6 +234,7 @@ class H2OSupportVectorMachineEstimator(ModelBuilder):
             coef = comm.all_gather_cat(coef)
         model = PSVMModel(self, model_id, sv_x.cpu(), coef.cpu(), b, gamma, means, scales)
         model.timings = {"ipm_iterations": iters, "icf_rank": int(H.shape[1]),
+                         "icf_engine": icf_engine(X, p, comm), "ipm_engine": ipm_engine(H),
                          "bounded_sv": int(_allsum(torch.tensor([float((alpha >= C - thr).sum())],
                                                                dtype=torch.float64, device=X.device), comm)[0])}
         return model
@@ -213,7 +243,8 @@ class H2OSupportVectorMachineEstimator(ModelBuilder):
         p_ = self.params
         n, k = H.shape
         dev = H.device
-        Hy = H * y[:, None]
+        hip = ipm_engine(H) == "hip"      # the products over H on the ops.svm kernels, Hy and Hd never materialised
+        Hy = None if hip else H * y[:, None]
         mu_f = float(p_["mu_factor"])
         alpha = C / 10.0
         lam = torch.ones(n, dtype=torch.float64, device=dev)     # multipliers of a >= 0
@@ -222,7 +253,10 @@ class H2OSupportVectorMachineEstimator(ModelBuilder):
         N = float(_allsum(torch.tensor([float(n)], dtype=torch.float64, device=dev), comm)[0])
         it = 0
         for it in range(1, int(p_["max_iterations"]) + 1):
-            Qa = Hy @ _allsum(Hy.t() @ alpha, comm)
+            if hip:
+                Qa = svm_ops.tall_v(H, y, _allsum(svm_ops.tall_tv(H, y, alpha[:, None]), comm))[:, 0]
+            else:
+                Qa = Hy @ _allsum(Hy.t() @ alpha, comm)
             gap_v = _allsum(torch.stack([(lam * alpha).sum() + (xi * (C - alpha)).sum(), (y * alpha).sum()]), comm)
             gap, ya = float(gap_v[0]), float(gap_v[1])
             rd = Qa - 1.0 + nu * y - lam + xi
@@ -234,8 +268,12 @@ class H2OSupportVectorMachineEstimator(ModelBuilder):
             z = -Qa + 1.0 - nu * y + mu / alpha - mu / (C - alpha)
             Dg = lam / alpha + xi / (C - alpha)
             # (Dg + Hy Hy^T)^-1 via Sherman-Morrison-Woodbury; M = I + Hy^T Dg^-1 Hy
-            Hd = Hy / Dg[:, None]
-            M = _allsum(Hy.t() @ Hd, comm)
+            if hip:
+                # y_i^2 = 1: Hy^T Dg^-1 Hy = H^T diag(1 / Dg) H
+                M = _allsum(svm_ops.wsyrk(H, 1.0 / Dg), comm)
+            else:
+                Hd = Hy / Dg[:, None]
+                M = _allsum(Hy.t() @ Hd, comm)
             M += torch.eye(k, dtype=torch.float64, device=dev)
             L = torch.linalg.cholesky(M)
 
@@ -243,7 +281,14 @@ class H2OSupportVectorMachineEstimator(ModelBuilder):
                 t = _allsum(Hd.t() @ v, comm)
                 return v / Dg - Hd @ torch.cholesky_solve(t[:, None], L)[:, 0]
 
-            Sz, Sy = solve(z), solve(y)
+            if hip:
+                # both right-hand sides in one pass over H each way: Hd = diag(y / Dg) H
+                yd = y / Dg
+                t = _allsum(svm_ops.tall_tv(H, yd, torch.stack([z, y], 1)), comm)
+                S = svm_ops.tall_v(H, yd, torch.cholesky_solve(t, L))
+                Sz, Sy = z / Dg - S[:, 0], yd - S[:, 1]
+            else:
+                Sz, Sy = solve(z), solve(y)
             s = _allsum(torch.stack([(y * Sz).sum(), (y * Sy).sum()]), comm)
             dnu = (float(s[0]) + ya) / float(s[1])
             da = Sz - dnu * Sy
