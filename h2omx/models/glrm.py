@@ -14,7 +14,10 @@ Alternating minimisation, every product on the fp32 matrix cores
 * with missing entries each row (X-step) / column (Y-step) has its own
   normal equations over its observed entries: batched k×k solves of
   Y diag(m_i) Yᵀ and X diag(m_j) Xᵀ (exact masked ALS), the column systems
-  all-reduced as one p×k×(k+1) tensor;
+  all-reduced as one p×k×(k+1) tensor.  On a device frame with k ≤ 32 both
+  come from ``ops.glrm`` (fp64 matrix-unit kernels, O(n p) memory, the row
+  systems solved inside the kernel); CPU frames and larger k build them as
+  torch expressions (:func:`als_engine`);
 * ``NonNegative`` projects onto X, Y ≥ 0 after each half-step and ``L1``
   soft-thresholds (proximal step); ``Quadratic`` / ``L2`` are the ridge
   terms above; ``None`` uses γ = 0.
@@ -35,6 +38,7 @@ import torch
 
 from ..frame.frame import DKV, Frame, Vec
 from ..backend import dense as D
+from ..ops import glrm as K
 from .base import Model, ModelBuilder, ModelCategory
 from .glm import DesignInfo
 from .pca import TRANSFORMS
@@ -114,15 +118,14 @@ def _ridge(reg: str, gamma: float) -> float:
     return gamma if reg.lower() in ("quadratic", "l2") else 0.0
 
 
-def _solve_x(A: torch.Tensor, mask: torch.Tensor, Y: torch.Tensor, p_) -> torch.Tensor:
-    """X [k][n] minimising the masked quadratic loss (+ x regulariser) with Y fixed."""
+def als_engine(A: torch.Tensor, k: int) -> str:
+    """Who builds the masked normal equations: the ``ops.glrm`` kernels or torch."""
+    return "hip" if A.is_cuda and k <= K.MAX_K else "torch"
+
+
+def _solve_x_torch(A: torch.Tensor, mask: torch.Tensor, Y: torch.Tensor, lam: float) -> torch.Tensor:
+    """Per-row normal equations over the observed columns, G_i = Y diag(m_i) Y^T, in chunks of rows."""
     k = Y.shape[0]
-    rx, gx = str(p_["regularization_x"]), float(p_["gamma_x"])
-    lam = _ridge(rx, gx) + 1e-8
-    if bool(mask.all()):
-        Gy = D.gemm(Y, Y, tb=True).double() + lam * torch.eye(k, dtype=torch.float64, device=Y.device)
-        return _prox(torch.linalg.inv(Gy.cpu()).to(Y.device, torch.float32) @ D.gemm(Y, A), rx, gx)
-    # per-row normal equations over the observed columns: G_i = Y diag(m_i) Y^T
     m = mask.float()
     out = torch.empty((k, A.shape[1]), dtype=torch.float32, device=A.device)
     eye = lam * torch.eye(k, dtype=torch.float64, device=A.device)
@@ -132,7 +135,32 @@ def _solve_x(A: torch.Tensor, mask: torch.Tensor, Y: torch.Tensor, p_) -> torch.
         G = torch.einsum("jn,aj,bj->nab", mb, Y, Y).double() + eye
         r = (Y @ (A[:, s0:s1] * mb)).T.double()                           # [n][k]
         out[:, s0:s1] = torch.linalg.solve(G, r.unsqueeze(-1)).squeeze(-1).T.float()
+    return out
+
+
+def _solve_x(A: torch.Tensor, mask: torch.Tensor, Y: torch.Tensor, p_) -> torch.Tensor:
+    """X [k][n] minimising the masked quadratic loss (+ x regulariser) with Y fixed."""
+    k = Y.shape[0]
+    rx, gx = str(p_["regularization_x"]), float(p_["gamma_x"])
+    lam = _ridge(rx, gx) + 1e-8
+    if bool(mask.all()):
+        Gy = D.gemm(Y, Y, tb=True).double() + lam * torch.eye(k, dtype=torch.float64, device=Y.device)
+        return _prox(torch.linalg.inv(Gy.cpu()).to(Y.device, torch.float32) @ D.gemm(Y, A), rx, gx)
+    if als_engine(A, k) == "hip":
+        out, bad = K.masked_x(A, mask, Y, lam)
+        if bad > 0:             # a singular row system: whatever the torch route makes of it
+            out = _solve_x_torch(A, mask, Y, lam)
+    else:
+        out = _solve_x_torch(A, mask, Y, lam)
     return _prox(out, rx, gx)
+
+
+def _solve_y_terms_torch(A: torch.Tensor, mask: torch.Tensor, X: torch.Tensor) -> torch.Tensor:
+    """S [p][k][k + 1] fp64, S[j] = [X diag(m_j) X^T | X (a_j m_j)]."""
+    m = mask.float()
+    G = torch.einsum("jn,an,bn->jab", m, X, X).double()                    # [p][k][k]
+    r = (X @ (A * m).T).T.double()                                         # [p][k]
+    return torch.cat([G, r.unsqueeze(-1)], -1)
 
 
 def _solve_y(A: torch.Tensor, mask: torch.Tensor, X: torch.Tensor, p_, comm, full: bool) -> torch.Tensor:
@@ -149,10 +177,7 @@ def _solve_y(A: torch.Tensor, mask: torch.Tensor, X: torch.Tensor, p_, comm, ful
             comm.all_reduce_(S)
         Gx = S[:, :k] + lam * torch.eye(k, dtype=torch.float64, device=dev)
         return _prox(torch.linalg.solve(Gx.cpu(), S[:, k:].cpu()).to(dev, torch.float32), ry, gy)
-    m = mask.float()
-    G = torch.einsum("jn,an,bn->jab", m, X, X).double()                    # [p][k][k]
-    r = (X @ (A * m).T).T.double()                                         # [p][k]
-    S = torch.cat([G, r.unsqueeze(-1)], -1)
+    S = K.masked_y_terms(A, mask, X) if als_engine(A, k) == "hip" else _solve_y_terms_torch(A, mask, X)
     if world > 1:
         comm.all_reduce_(S)
     G = S[..., :k] + lam * torch.eye(k, dtype=torch.float64, device=dev)
@@ -242,6 +267,7 @@ class H2OGeneralizedLowRankEstimator(ModelBuilder):
         model.scoring_history = hist
         model.training_metrics = {"objective": obj, "iterations": it, "numerr": float(parts[0]),
                                   "nobs": float(nobs), "caterr": 0.0}
+        model.timings["als_engine"] = "gemm" if full else als_engine(A, k)
         rep = Frame([Vec(f"Arch{i + 1}", X[i].float(), "real") for i in range(k)],
                     key=p_["representation_name"] or None)
         DKV.put(rep.key, rep)
