@@ -1,7 +1,8 @@
 // PSVM on gfx950, all fp64: the pivoted incomplete Cholesky factorisation of the
 // Gaussian kernel with its state on the device, the weighted symmetric product
 // C = A^T diag(w) A of the interior-point Newton system on
-// v_mfma_f64_16x16x4_f64, and the two thin products of its solves.
+// v_mfma_f64_16x16x4_f64, the two thin products of its solves, and the decision
+// function of the fitted model with the kernel values kept in registers.
 //
 //   icf_init_kernel     diag = 1, first pivot candidate (row 0), empty record
 //   icf_pivot_kernel    one workgroup: arg-max of the block partials (ties to the
@@ -12,6 +13,10 @@
 //   tall_tv_kernel      A^T diag(s) V, r <= 4 columns, slab partials
 //   tall_fold_kernel    slabs added in slab order
 //   tall_v_kernel       diag(s) A T, r <= 4 columns
+//   rbf_sqnorm_kernel   fp64 squared row norms of an fp32 matrix
+//   rbf_decision_kernel sum_j coef_j exp(-gamma |x_i - s_j|^2) for 64 rows over one
+//                       slab of support vectors
+//   rbf_decision_fold_kernel  slabs added in slab order
 //
 // Nothing here uses a floating-point atomic or waits for another workgroup;
 // every sum has a fixed order, so results are bit-identical between calls.
@@ -32,6 +37,27 @@
 // A diagonal block reads its panel from global memory once and writes the
 // weighted and the plain copy; its wave below the diagonal only stages.  Columns
 // past k and rows past the slab are zero in the stage.
+//
+// rbf_decision.  A workgroup of four waves owns 64 scored rows and walks one slab
+// of support vectors in tiles of 64.  The cross term C = S_tile X_block^T runs on
+// the matrix units with the wsyrk wave layout (C rows are SVs, C columns scored
+// rows), so a lane owns the scored rows lane % 16 of its two column tiles and four
+// SVs per accumulator.  The fp32 inputs are widened to fp64 on their way into LDS,
+// which is exact: every product is exact and only the additions round.  The
+// features are walked in chunks of 16; the stage is [feature][point], 80 doubles a
+// row as above, and a thread stages four adjacent features of one point (lanes
+// along points, so the transposed LDS writes are consecutive).  Up to kRbfResD
+// features the X block is staged once and stays in LDS for the whole slab
+// (kResident); above, its chunks are staged again for every SV tile next to those
+// of S.  The SV chunks are double buffered over the flattened (tile, chunk)
+// sequence: global loads of the next step before the matrix instructions of this
+// one, LDS writes after, one barrier per step.  A tile's |s_j|^2 and coef_j travel
+// with its first chunk into a stage of their own, alternating by tile.  After a
+// tile's last chunk the epilogue stays in registers: d2 = |x_i|^2 + |s_j|^2 - 2 c
+// clamped at 0, exp, times coef_j, added into one running sum per lane and column
+// tile in a fixed order.  At the slab's end the four lane groups are added by
+// cross-lane moves and the two waves that share rows through LDS.  Ragged rows,
+// SVs and features are zeros in the stage, padded SVs carry coef = 0.
 #include "common.h"
 
 namespace {
@@ -46,6 +72,7 @@ constexpr int kLd = 80;              // wsyrk LDS row, doubles
 constexpr int kTChunk = 1024;        // tall_v: rows of T per LDS stage
 constexpr int kTvUnitRows = 4;       // tall_v: rows per unit
 constexpr int kMaxR = 4;             // thin products: right-hand sides
+constexpr int kRbfResD = 32;         // rbf_decision: features of the resident X block
 
 typedef double d4 __attribute__((ext_vector_type(4)));
 
@@ -362,6 +389,164 @@ __global__ __launch_bounds__(kThreads) void tall_v_kernel(const double* __restri
   }
 }
 
+// ------------------------------------------------------------- rbf decision
+
+__global__ __launch_bounds__(kThreads) void rbf_sqnorm_kernel(const float* __restrict__ A, int64_t n, int d,
+                                                              double* __restrict__ out) {
+  const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+  if (i >= n) return;
+  const float* a = A + i * d;
+  double s = 0.0;
+  for (int j = 0; j < d; ++j) s += (double)a[j] * (double)a[j];
+  out[i] = s;
+}
+
+// dst[slab][n]; one slab: dst is the result
+template <bool kResident>
+__global__ __launch_bounds__(kThreads) void rbf_decision_kernel(
+    const float* __restrict__ X, const float* __restrict__ S, const double* __restrict__ coef,
+    const double* __restrict__ xsq, const double* __restrict__ ssq, int64_t n, int64_t nsv, int d, int64_t slab_svs,
+    double gamma, double* __restrict__ dst) {
+  __shared__ double sS[2][kChunk * kLd];
+  __shared__ double sX[kResident ? kRbfResD / kChunk : 2][kChunk * kLd];
+  __shared__ double sQ[2][kBlk], sCf[2][kBlk];   // |s_j|^2 and coef_j of a tile, by tile parity
+  __shared__ double sF[4][32];
+  const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
+  const int tr = (wave >> 1) * 2, tc = (wave & 1) * 2;
+  const int64_t i0 = (int64_t)blockIdx.x * kBlk;
+  const int64_t j0 = (int64_t)blockIdx.y * slab_svs;
+  const int64_t j1 = j0 + slab_svs < nsv ? j0 + slab_svs : nsv;
+  const int nch = (d + kChunk - 1) / kChunk;
+  const int sp = tid & (kBlk - 1), sf = (tid / kBlk) * 4;   // stage: point, first feature of the chunk
+  const bool okx = i0 + sp < n;
+  const float* xrow = X + (i0 + sp) * d;
+  float gs[4], gx[4];
+  double gq = 0.0, gc = 0.0;
+  auto load_x = [&](int c) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int col = c * kChunk + sf + q;
+      gx[q] = (okx && col < d) ? xrow[col] : 0.f;
+    }
+  };
+  auto store_x = [&](double* sx) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) sx[(sf + q) * kLd + sp] = (double)gx[q];
+  };
+  auto load_s = [&](int64_t t0, int c) {
+    const int64_t j = t0 + sp;
+    const bool ok = j < j1;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int col = c * kChunk + sf + q;
+      gs[q] = (ok && col < d) ? S[j * d + col] : 0.f;
+    }
+    if (c == 0 && tid < kBlk) {
+      gq = ok ? ssq[j] : 0.0;
+      gc = ok ? coef[j] : 0.0;
+    }
+  };
+  auto store_s = [&](int b, int c, int par) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) sS[b][(sf + q) * kLd + sp] = (double)gs[q];
+    if (c == 0 && tid < kBlk) {
+      sQ[par][tid] = gq;
+      sCf[par][tid] = gc;
+    }
+  };
+  if (kResident) {
+    for (int c = 0; c < nch; ++c) {
+      load_x(c);
+      store_x(sX[c]);
+    }
+  } else {
+    load_x(0);
+    store_x(sX[0]);
+  }
+  load_s(j0, 0);
+  store_s(0, 0, 0);
+  const int64_t ra = i0 + tc * 16 + (lane & 15);
+  const double xs0 = ra < n ? xsq[ra] : 0.0, xs1 = ra + 16 < n ? xsq[ra + 16] : 0.0;
+  const double ng = -gamma;
+  __syncthreads();
+  d4 c00 = {0, 0, 0, 0}, c01 = c00, c10 = c00, c11 = c00;
+  double f0 = 0.0, f1 = 0.0;
+  const int oa = tr * 16 + (lane & 15), ob = tc * 16 + (lane & 15);
+  int b = 0, c = 0, par = 0;
+  int64_t t0 = j0;
+  for (;;) {
+    int cn = c + 1;
+    int64_t tn = t0;
+    if (cn == nch) { cn = 0; tn += kBlk; }
+    const bool more = tn < j1;
+    if (more) {
+      load_s(tn, cn);
+      if (!kResident) load_x(cn);
+    }
+    const double* sx = kResident ? sX[c] : sX[b];
+    const int ks = (d - c * kChunk + 3) / 4;
+#pragma unroll
+    for (int kk = 0; kk < kChunk / 4; ++kk) {
+      if (kk >= ks) break;
+      const int ro = (4 * kk + (lane >> 4)) * kLd;
+      const double a0 = sS[b][ro + oa], a1 = sS[b][ro + oa + 16];
+      const double b0 = sx[ro + ob], b1 = sx[ro + ob + 16];
+      c00 = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b0, c00, 0, 0, 0);
+      c01 = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b1, c01, 0, 0, 0);
+      c10 = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b0, c10, 0, 0, 0);
+      c11 = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b1, c11, 0, 0, 0);
+    }
+    if (c == nch - 1) {
+      // register v of a tile holds C[4 v + lane / 16][lane % 16]: SV 4 v + lane / 16, scored row lane % 16
+#pragma unroll
+      for (int v = 0; v < 4; ++v) {
+        const int j = tr * 16 + 4 * v + (lane >> 4);
+        const double q0 = sQ[par][j], q1 = sQ[par][j + 16];
+        const double w0 = sCf[par][j], w1 = sCf[par][j + 16];
+        double e;
+        e = xs0 + q0 - 2.0 * c00[v]; f0 += w0 * exp(ng * (e > 0.0 ? e : 0.0));
+        e = xs1 + q0 - 2.0 * c01[v]; f1 += w0 * exp(ng * (e > 0.0 ? e : 0.0));
+        e = xs0 + q1 - 2.0 * c10[v]; f0 += w1 * exp(ng * (e > 0.0 ? e : 0.0));
+        e = xs1 + q1 - 2.0 * c11[v]; f1 += w1 * exp(ng * (e > 0.0 ? e : 0.0));
+      }
+      c00 = d4{0, 0, 0, 0}; c01 = c00; c10 = c00; c11 = c00;
+    }
+    if (more) {
+      store_s(b ^ 1, cn, par ^ 1);
+      if (!kResident) store_x(sX[b ^ 1]);
+    }
+    __syncthreads();
+    if (!more) break;
+    b ^= 1;
+    if (cn == 0) par ^= 1;
+    c = cn;
+    t0 = tn;
+  }
+  // the four lane groups, then the two waves that share the rows
+  f0 += __shfl_xor(f0, 16, kWave);
+  f1 += __shfl_xor(f1, 16, kWave);
+  f0 += __shfl_xor(f0, 32, kWave);
+  f1 += __shfl_xor(f1, 32, kWave);
+  if (lane < 16) {
+    sF[wave][lane] = f0;
+    sF[wave][lane + 16] = f1;
+  }
+  __syncthreads();
+  if (tid < kBlk && i0 + tid < n) {
+    const int h = tid >> 5, r = tid & 31;
+    dst[(int64_t)blockIdx.y * n + i0 + tid] = sF[h][r] + sF[h + 2][r];
+  }
+}
+
+__global__ __launch_bounds__(kThreads) void rbf_decision_fold_kernel(const double* __restrict__ part, int slabs,
+                                                                     int64_t n, double* __restrict__ out) {
+  const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+  if (i >= n) return;
+  double t = 0.0;
+  for (int q = 0; q < slabs; ++q) t += part[(int64_t)q * n + i];
+  out[i] = t;
+}
+
 int unit_lanes(int len) {   // power of two, 1 .. 64, covering len where it can
   int v = 1;
   while (v < len && v < kWave) v <<= 1;
@@ -429,5 +614,29 @@ H2OMX_API int h2omx_svm_tall_v(const double* A, const double* s, const double* T
   const int U = unit_lanes(k);
   const int64_t rows = (int64_t)(kThreads / U) * kTvUnitRows;
   tall_v_kernel<<<(unsigned)((n + rows - 1) / rows), kThreads, 0, stream>>>(A, s, T, n, k, r, U, out);
+  return launch_status();
+}
+
+// out [n] = sum_j coef_j exp(-gamma |x_i - s_j|^2) for X [n][d] and S [nsv][d] fp32, coef [nsv] fp64,
+// gamma > 0.  Work: xsq [n], ssq [nsv]; part [slabs][n] with slabs = ceil(nsv / slab_svs), unused
+// (may be null) with one slab.
+H2OMX_API int h2omx_svm_rbf_decision(const float* X, const float* S, const double* coef, int64_t n, int64_t nsv, int d,
+                                     double gamma, int64_t slab_svs, double* xsq, double* ssq, double* part,
+                                     double* out, hipStream_t stream) {
+  if (n < 1 || nsv < 1 || d < 1 || slab_svs < 1 || !(gamma > 0.0)) return kBadArg;
+  const int64_t slabs = (nsv + slab_svs - 1) / slab_svs;
+  const int64_t blocks = (n + kBlk - 1) / kBlk;
+  if (slabs > 65535 || blocks > INT32_MAX) return kBadArg;
+  rbf_sqnorm_kernel<<<(unsigned)((n + kThreads - 1) / kThreads), kThreads, 0, stream>>>(X, n, d, xsq);
+  rbf_sqnorm_kernel<<<(unsigned)((nsv + kThreads - 1) / kThreads), kThreads, 0, stream>>>(S, nsv, d, ssq);
+  double* dst = slabs > 1 ? part : out;
+  const dim3 grid((unsigned)blocks, (unsigned)slabs);
+  if (d <= kRbfResD)
+    rbf_decision_kernel<true><<<grid, kThreads, 0, stream>>>(X, S, coef, xsq, ssq, n, nsv, d, slab_svs, gamma, dst);
+  else
+    rbf_decision_kernel<false><<<grid, kThreads, 0, stream>>>(X, S, coef, xsq, ssq, n, nsv, d, slab_svs, gamma, dst);
+  if (slabs > 1)
+    rbf_decision_fold_kernel<<<(unsigned)((n + kThreads - 1) / kThreads), kThreads, 0, stream>>>(part, (int)slabs, n,
+                                                                                                 out);
   return launch_status();
 }

@@ -27,8 +27,11 @@ This is a binary kernel SVM trained with the PSVM scheme (Chang et al.,
    duality gap and the primal / dual residuals are below their thresholds.
 3. Support vectors are rows with a_i > sv_threshold.  The bias b is averaged
    over the free support vectors, 0 < a_i < C_i.
-Scoring: f(x) = sum_sv a_i y_i K(x_i, x) + b.  The cross term x . sv is the
-fp32 MFMA GEMM of ops.dense.gemm, with the squared norms and exp fused after it.
+Scoring: f(x) = sum_sv a_i y_i K(x_i, x) + b.  On a device frame this is
+ops.svm.rbf_decision: the cross term x . sv on the fp64 matrix units, the squared
+norms, exp and the sum over the support vectors in registers, so no
+[rows][nsv] block exists.  On a CPU frame the cross term is ops.dense.gemm in
+fp32 over 65536 rows at a time, with the squared norms and exp applied after it.
 """
 from __future__ import annotations
 
@@ -75,6 +78,11 @@ def icf(X: torch.Tensor, gamma: float, p: int, thresh: float, comm=None) -> torc
 def ipm_engine(H: torch.Tensor) -> str:
     """``"hip"`` where the interior point takes its products over H from the ops.svm kernels."""
     return "hip" if H.is_cuda else "torch"
+
+
+def score_engine(X: torch.Tensor) -> str:
+    """``"hip"`` where decision_function runs on ops.svm.rbf_decision."""
+    return "hip" if X.is_cuda else "torch"
 
 
 def _icf_torch(X: torch.Tensor, gamma: float, p: int, thresh: float, comm=None) -> torch.Tensor:
@@ -139,6 +147,15 @@ class PSVMModel(Model):
         dev = X.device
         if self.sv.shape[0] == 0:
             return torch.full((X.shape[0],), self.b, device=dev)
+        if score_engine(X) == "hip":
+            out = svm_ops.rbf_decision(X, self.sv.to(dev), self.coef.to(dev), self.gamma)
+        else:
+            out = self._decision_torch(X)
+        return (out + self.b).float()
+
+    def _decision_torch(self, X: torch.Tensor) -> torch.Tensor:
+        """sum_sv a_i y_i K(x_i, x) over [65536][nsv] blocks, fp64 [n]."""
+        dev = X.device
         S = self.sv.to(dev)
         out = torch.zeros(X.shape[0], dtype=torch.float64, device=dev)
         ssq = (S.double() * S.double()).sum(1)
@@ -149,7 +166,7 @@ class PSVMModel(Model):
             G = D.gemm(xb, S, tb=True)                                   # [rows][nsv] x . sv
             d2 = ((xb.double() * xb.double()).sum(1)[:, None] - 2.0 * G.double() + ssq[None, :]).clamp_min(0.0)
             out[r0:r0 + step] = torch.exp(-self.gamma * d2) @ coef
-        return (out + self.b).float()
+        return out
 
     def predict_raw(self, frame: Frame) -> torch.Tensor:
         f = self.decision_function(frame)
@@ -235,6 +252,7 @@ class H2OSupportVectorMachineEstimator(ModelBuilder):
         model = PSVMModel(self, model_id, sv_x.cpu(), coef.cpu(), b, gamma, means, scales)
         model.timings = {"ipm_iterations": iters, "icf_rank": int(H.shape[1]),
                          "icf_engine": icf_engine(X, p, comm), "ipm_engine": ipm_engine(H),
+                         "score_engine": score_engine(X),
                          "bounded_sv": int(_allsum(torch.tensor([float((alpha >= C - thr).sum())],
                                                                dtype=torch.float64, device=X.device), comm)[0])}
         return model

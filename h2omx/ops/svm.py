@@ -1,8 +1,10 @@
-"""Python entry points of csrc/svm_kernels.hip (PSVM: ICF, interior-point products).
+"""Python entry points of csrc/svm_kernels.hip (PSVM: ICF, interior-point products,
+decision function).
 
-Device tensors only, all fp64; every launch goes to the current stream.  Every
-result is bit-identical between two calls: no floating-point atomics, slab
-partials added in slab order.
+Device tensors only, all fp64 (rbf_decision: fp32 points, fp64 coefficients and
+result); every launch goes to the current stream.  Every result is
+bit-identical between two calls: no floating-point atomics, slab partials added
+in slab order.
 """
 from __future__ import annotations
 
@@ -21,6 +23,8 @@ SVM_SIGS = {
     "h2omx_svm_tall_tv": "PPPLIILPPS",
     # A, s, T, n, k, r, out
     "h2omx_svm_tall_v": "PPPLIIPS",
+    # X, S, coef, n, nsv, d, gamma, slab_svs, xsq, ssq, part, out
+    "h2omx_svm_rbf_decision": "PPPLLIDLPPPPS",
 }
 
 # limits of the ICF kernels (LDS stage of the pivot row: 8 KB of x, 32 KB of H)
@@ -34,6 +38,11 @@ WSYRK_FILL = 4
 # ... unless the slab partials would pass 1 / 8 of the n k doubles of A
 WSYRK_PART_SHARE = 8
 TALL_TV_BLOCKS = 2048
+RBF_BLOCK = 64               # scored rows of a workgroup, SVs of a tile
+# rbf_decision: (row blocks x slabs) fills the compute units this many times over ...
+RBF_FILL = 4
+# ... unless the slab partials would pass the bytes of X, S and coef
+RBF_PART_SHARE = 1
 MAX_SLABS = 65535
 
 
@@ -143,4 +152,46 @@ def tall_v(A: torch.Tensor, s: torch.Tensor | None, T: torch.Tensor) -> torch.Te
     if n == 0:
         return out
     check(svm_lib().h2omx_svm_tall_v(P(A), P(s), P(T), n, k, r, P(out), stream(dev)), "svm_tall_v")
+    return out
+
+
+def rbf_slab_svs(n: int, nsv: int, d: int, cus: int) -> int:
+    """Support vectors per slab, a multiple of 64: enough slabs for row blocks
+    x slabs to fill the machine RBF_FILL times over, capped so the [slab][n]
+    fp64 partials stay within 1 / RBF_PART_SHARE of the bytes of X, S and coef."""
+    blocks = -(-n // RBF_BLOCK)
+    slabs = -(-RBF_FILL * cus // blocks)
+    cap = (4 * (n + nsv) * d + 8 * nsv) // RBF_PART_SHARE // (8 * n)
+    slabs = max(1, min(slabs, cap, -(-nsv // RBF_BLOCK), MAX_SLABS))
+    return -(-(-(-nsv // slabs)) // RBF_BLOCK) * RBF_BLOCK
+
+
+def rbf_decision(X: torch.Tensor, S: torch.Tensor, coef: torch.Tensor, gamma: float,
+                 slab_svs: int | None = None) -> torch.Tensor:
+    """``f_i = sum_j coef_j exp(-gamma |x_i - s_j|^2)`` -> fp64 [n] for fp32 points
+    X [n][d] and S [nsv][d] and fp64 coef [nsv]: the cross term on the fp64
+    matrix units, exp and the sum over j in registers.  No [n][nsv] tensor
+    exists; the memory beyond the result is the row norms (n + nsv doubles) and
+    the [slabs][n] partials."""
+    if not (X.is_cuda and S.is_cuda and coef.is_cuda):
+        raise ValueError("ops.svm.rbf_decision: device tensors only")
+    if X.dim() != 2 or S.dim() != 2 or X.shape[1] < 1 or S.shape[1] != X.shape[1] or coef.shape != (S.shape[0],):
+        raise ValueError("ops.svm.rbf_decision: X [n][d], S [nsv][d] with d >= 1 and coef [nsv]")
+    n, d = X.shape
+    nsv = S.shape[0]
+    if nsv < 1 or not gamma > 0:
+        raise ValueError(f"ops.svm.rbf_decision: nsv={nsv} gamma={gamma}, the kernel takes nsv >= 1 and gamma > 0")
+    X, S = X.to(torch.float32).contiguous(), S.to(torch.float32).contiguous()
+    coef = coef.to(torch.float64).contiguous()
+    dev = X.device
+    out = _empty(n, dev)
+    if n == 0:
+        return out
+    if slab_svs is None:
+        slab_svs = rbf_slab_svs(n, nsv, d, torch.cuda.get_device_properties(dev).multi_processor_count)
+    slabs = -(-nsv // slab_svs)
+    xsq, ssq = _empty(n, dev), _empty(nsv, dev)
+    part = _empty((slabs, n), dev) if slabs > 1 else None
+    check(svm_lib().h2omx_svm_rbf_decision(P(X), P(S), P(coef), n, nsv, d, float(gamma), slab_svs, P(xsq), P(ssq),
+                                           P(part), P(out), stream(dev)), "svm_rbf_decision")
     return out
