@@ -30,12 +30,14 @@ KERNEL_LIBS = {
     "survival": ["cox_kernels.hip"],
     "svm": ["svm_kernels.hip"],
     "glrm": ["glrm_kernels.hip"],
+    "eif": ["eif_kernels.hip"],
 }
-# library name -> extra compiler flags (svm, glrm: no packed fp32 instructions)
+# library name -> extra compiler flags (svm, glrm, eif: no packed fp32 instructions)
 _NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 KERNEL_FLAGS = {
     "svm": _NO_PACKED_FP32,
     "glrm": _NO_PACKED_FP32,
+    "eif": _NO_PACKED_FP32,
 }
 HOST_LIBS = {
     "host": ["host/parser.cpp", "host/solvers.cpp"],

@@ -9,7 +9,10 @@ Trees grow to depth ceil(log2(sample_size)).
 
 Training samples are drawn per rank (its share of the global sample, seeded
 by (seed, tree, rank)) and all-gathered once, so every rank builds the same
-small trees on the host.  Scoring is GEMM-shaped: the hyperplane offsets of
+small trees on the host.  Scoring a device frame is ops.anomaly.eif_mean_length:
+every row walks every tree on the csrc/eif_kernels.hip kernels, which form only
+the hyperplane products on its own path (exact fp64 products of the fp32
+values).  Scoring a CPU frame is GEMM-shaped: the hyperplane offsets of
 every node of a block of trees are ONE fp32 matrix-core product X·Nᵀ
 (ops.dense.gemm) per row block, after which rows walk their trees with
 gathers.  Path length = depth + c(leaf size); outputs ``anomaly_score`` =
@@ -24,6 +27,7 @@ import torch
 
 from ..frame.frame import Frame, Vec
 from ..backend import dense as D
+from ..ops import anomaly as anomaly_ops
 from .base import Model, ModelBuilder, ModelCategory
 from .glm import DesignInfo
 from .isolation_forest import avg_path
@@ -76,7 +80,31 @@ class ExtendedIsolationForestModel(Model):
         self.limit = limit
         self.sample_size = sample_size
 
-    def mean_length(self, frame: Frame, block: int = 8192, tree_block: int = 32) -> torch.Tensor:
+    def score_engine(self, frame: Frame) -> str:
+        """``"hip"`` where mean_length runs on the ops.anomaly walk kernels: a device frame
+        and a forest they take (sparse walk: any width; dense walk: up to 256 columns)."""
+        if not frame.device.type == "cuda" or self.limit > anomaly_ops.EIF_MAX_LIMIT:
+            return "torch"
+        T, _, p = self.normals.shape
+        if p < 1 or not 1 <= T <= anomaly_ops.EIF_MAX_TREES:
+            return "torch"
+        if "_eif_k" not in self.__dict__:
+            self._eif_k = int((self.normals != 0).sum(-1).max())
+        return "torch" if self._eif_k > anomaly_ops.EIF_SPARSE_MAX_K and p > anomaly_ops.EIF_DENSE_MAX_P else "hip"
+
+    def _plan(self, device):
+        plans = self.__dict__.setdefault("_eif_plans", {})
+        key = str(device)
+        if key not in plans:
+            plans[key] = anomaly_ops.eif_pack(self.normals, self.offs, self.sizes, self.design.means, device)
+        return plans[key]
+
+    def mean_length(self, frame: Frame) -> torch.Tensor:
+        if self.score_engine(frame) == "hip":
+            return anomaly_ops.eif_mean_length(self.design.raw_matrix(frame), self._plan(frame.device))
+        return self._mean_length_torch(frame)
+
+    def _mean_length_torch(self, frame: Frame, block: int = 8192, tree_block: int = 32) -> torch.Tensor:
         Xraw = self.design.raw_matrix(frame)
         dev = Xraw.device
         m = torch.from_numpy(self.design.means.astype(np.float32)).to(dev)[:, None]
@@ -179,4 +207,5 @@ class H2OExtendedIsolationForestEstimator(ModelBuilder):
             model.training_metrics = {"mean_length": float(ml.mean()), "nobs": N}
         else:
             model.training_metrics = {"nobs": N}
+        model.timings = {"score_engine": model.score_engine(train)}
         return model
