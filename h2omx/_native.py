@@ -31,13 +31,16 @@ KERNEL_LIBS = {
     "svm": ["svm_kernels.hip"],
     "glrm": ["glrm_kernels.hip"],
     "eif": ["eif_kernels.hip"],
+    "uplift": ["uplift_kernels.hip"],
 }
-# library name -> extra compiler flags (svm, glrm, eif: no packed fp32 instructions)
+# library name -> extra compiler flags (svm, glrm, eif, uplift: no packed fp32 instructions; uplift also without
+# floating-point contraction, its gains round as the tensor expressions they replace)
 _NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 KERNEL_FLAGS = {
     "svm": _NO_PACKED_FP32,
     "glrm": _NO_PACKED_FP32,
     "eif": _NO_PACKED_FP32,
+    "uplift": _NO_PACKED_FP32 + ["-ffp-contract=off"],
 }
 HOST_LIBS = {
     "host": ["host/parser.cpp", "host/solvers.cpp"],

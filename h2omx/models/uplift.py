@@ -20,7 +20,10 @@ control responders.  Each histogram is a float64 bincount; across ranks they
 are summed with one all-reduce.  The split scan runs as vectorised tensor ops
 over every (node, feature, bin, NA direction).  A child needs ``min_rows`` rows
 and at least one treated and one control row.  Leaves store (p_t, p_c).
-Prediction averages both over the trees.
+Prediction averages both over the trees.  On a device frame the histograms
+(int32 counts), the split scan, the row routing and the scoring run on the
+``ops.uplift`` kernels instead (``tree_engine`` / ``score_engine`` name the
+route); among equal gains the lowest (na_left, feature, bin) wins.
 
 Output columns match H2O: ``uplift_predict``, ``p_y1_with_treatment`` and
 ``p_y1_without_treatment``.
@@ -45,6 +48,7 @@ import numpy as np
 import torch
 
 from ..frame.frame import ENUM, Frame, Vec
+from ..ops import uplift as uplift_ops
 from .base import Model, ModelBuilder, ModelCategory
 from .tree import bin_matrix, compute_edges
 
@@ -193,7 +197,31 @@ class UpliftDRFModel(Model):
         X = frame.feature_matrix(self.x)
         return bin_matrix(X, self.edges, self.nvb, self.nbt, names=self.x)
 
+    def score_engine(self, frame: Frame) -> str:
+        """``"hip"`` where predict_raw runs on ops.uplift.forest_predict: a device frame
+        whose binned matrix and forest the kernel takes."""
+        ok = (frame.device.type == "cuda" and len(self.trees) >= 1 and self.nbt <= uplift_ops.MAX_NBT
+              and 1 <= len(self.x) <= uplift_ops.MAX_F and 1 <= frame.nrows <= uplift_ops.MAX_ROWS
+              and int(self.params.get("max_depth") or 0) <= uplift_ops.MAX_DEPTH)
+        return "hip" if ok else "torch"
+
+    def _plan(self, device):
+        plans = self.__dict__.setdefault("_uplift_plans", {})
+        key = str(device)
+        if key not in plans:
+            plans[key] = uplift_ops.pack_forest(self.trees, device, self.nbt)
+        return plans[key]
+
     def predict_raw(self, frame: Frame) -> torch.Tensor:
+        if self.score_engine(frame) != "hip":
+            return self._predict_raw_torch(frame)
+        bm = self._codes(frame)
+        pt, pc = uplift_ops.forest_predict(bm.codes, self._plan(bm.device), frame.nrows)
+        k = max(len(self.trees), 1)
+        pt, pc = (pt / k).float(), (pc / k).float()
+        return torch.stack([pt - pc, pt, pc]).to(frame.device)
+
+    def _predict_raw_torch(self, frame: Frame) -> torch.Tensor:
         bm = self._codes(frame)
         n = frame.nrows
         pt = torch.zeros(n, dtype=torch.float64, device=bm.device)
@@ -323,10 +351,41 @@ class H2OUpliftRandomForestEstimator(ModelBuilder):
             trees.append(self._grow(codes, rc, F, nbt, bin_ok, tree_cols, mtries, g_feat, metric, min_rows, msi,
                                     comm))
         model = UpliftDRFModel(self, model_id, trees, np.asarray(edges), nvb_np, nbt, tc)
+        model.timings = {"tree_engine": self.tree_engine(codes), "score_engine": model.score_engine(train)}
         return model
 
+    def tree_engine(self, codes: torch.Tensor) -> str:
+        """``"hip"`` where the trees grow on the ops.uplift kernels: device codes of at most
+        256 bins and 32767 features, and int32 counts.  With several ranks the bound on
+        the summed row count is this rank's rows times the number of ranks, as no
+        collective is spent on it.  The choice has to be the same on every rank; it can
+        differ only where the shards are uneven and one of them is within a factor of
+        the rank count of 2^31 rows, and such a fit has to even out its shards."""
+        world = self.comm.world_size if getattr(self, "comm", None) is not None else 1
+        F, n = codes.shape
+        # uint8 codes: nbt <= 256 holds by construction
+        ok = (codes.is_cuda and codes.dtype == torch.uint8 and 1 <= F <= uplift_ops.MAX_F
+              and 1 <= n and n * world <= uplift_ops.MAX_ROWS)
+        return "hip" if ok else "torch"
+
+    def _grow(self, codes, rc, F, nbt, bin_ok, tree_cols, mtries, g_feat, metric, min_rows, msi, comm):
+        grow = self._grow_hip if self.tree_engine(codes) == "hip" else self._grow_torch
+        return grow(codes, rc, F, nbt, bin_ok, tree_cols, mtries, g_feat, metric, min_rows, msi, comm)
+
     @staticmethod
-    def _hist(codes, rc, slot, S, F, nbt, comm):
+    def _hist_hip(codes, key, S, nbt, comm):
+        """Category counts int32 [S][F][nbt][4] of the rows with key = slot * 4 + category
+        >= 0.  Several ranks: summed as fp64 by the all-reduce of the tensor route, which
+        is exact, and cast back."""
+        H = uplift_ops.category_hist(codes, key, S, nbt)
+        if comm is not None and comm.world_size > 1:
+            Hd = H.double()
+            comm.all_reduce_(Hd)
+            H = Hd.to(torch.int32)
+        return H
+
+    @staticmethod
+    def _hist_torch(codes, rc, slot, S, F, nbt, comm):
         """Category counts [S][F][nbt][4] of the rows with slot >= 0: one
         unweighted bincount over (slot, feature, bin, category) keys."""
         dev = codes.device
@@ -344,7 +403,9 @@ class H2OUpliftRandomForestEstimator(ModelBuilder):
             comm.all_reduce_(H)
         return H.view(S, F, nbt, 4)
 
-    def _grow(self, codes, rc, F, nbt, bin_ok, tree_cols, mtries, g_feat, metric, min_rows, msi, comm):
+    _hist = _hist_torch       # the unchanged body of _grow_torch calls self._hist
+
+    def _grow_torch(self, codes, rc, F, nbt, bin_ok, tree_cols, mtries, g_feat, metric, min_rows, msi, comm):
         """Level-wise tree on category counts; each level builds the histogram
         of the smaller child of every split and derives its sibling by
         subtraction from the parent."""
@@ -439,6 +500,73 @@ class H2OUpliftRandomForestEstimator(ModelBuilder):
             Hpar = Hc[torch.tensor(parent, dtype=torch.long, device=dev)]
             Hs = Hpar - Hb
             Hn = torch.empty((2 * P, F, nbt, 4), dtype=torch.float64, device=dev)
+            pidx = torch.arange(P, device=dev)
+            Hn[2 * pidx + br] = Hb
+            Hn[2 * pidx + 1 - br] = Hs
+            Hc = Hn
+            level_nodes = new_nodes
+        arr = tree.arrays()
+        arr["gain"] = np.array(gains, np.float64)
+        return arr
+
+    def _grow_hip(self, codes, rc, F, nbt, bin_ok, tree_cols, mtries, g_feat, metric, min_rows, msi, comm):
+        """_grow_torch on the ops.uplift kernels: the same control flow, host bookkeeping
+        and random draws; histograms, split scan and routing are one launch each per
+        level, and the counts stay int32."""
+        dev = codes.device
+        max_depth = int(self.params["max_depth"])
+        tree = UpliftTree()
+        gains = [0.0]
+        cat = rc.to(torch.int32)                                            # -1 = out of bag
+        nid = torch.where(cat >= 0, torch.zeros_like(cat), torch.full_like(cat, -1))   # level-local node, -1 = done
+        nvb = (bin_ok.sum(1) + 1).to(torch.int32)
+        Hc = self._hist_hip(codes, cat, 1, nbt, comm)                       # root: slot 0, key = category
+        tot0 = Hc[0, 0].sum(0).cpu().numpy().astype(np.float64)
+        root_t = tot0[0] + tot0[1]
+        root_c = tot0[2] + tot0[3]
+        tree.add(tot0[1] / root_t if root_t > 0 else 0.0, tot0[3] / root_c if root_c > 0 else 0.0)
+        level_nodes = [0]
+        for depth in range(max_depth):
+            K = len(level_nodes)
+            fmask = tree_cols.clone()[None, :].repeat(K, 1)
+            if mtries < F:
+                r = torch.rand((K, F), generator=g_feat)
+                r[~fmask] = 2.0
+                kth = torch.topk(r, mtries, dim=1, largest=False).values[:, -1:]
+                fmask = r <= kth
+            rec_d = uplift_ops.best_splits(Hc, fmask.to(dev), nvb, metric, min_rows)
+            rec = uplift_ops.split_records(rec_d)                           # the level's one host read
+            gain_c = rec["gain"]
+            split_c = np.isfinite(gain_c) & (gain_c > msi)
+            if not split_c.any():
+                break
+            best_c = np.stack([rec["feat"], rec["bin"], rec["na_left"]], 1)
+            Lc, tot_c = rec["left"].T.astype(np.float64), rec["node"].T.astype(np.float64)
+            Rc = tot_c - Lc
+            new_nodes, parent, built_right = [], [], []
+            remap = np.full(K, -1, np.int32)
+            for k in np.nonzero(split_c)[0]:
+                node = level_nodes[k]
+                pt, pc = tree.pt[node], tree.pc[node]
+                lt, lc = Lc[:, k], Rc[:, k]
+                li = tree.add(lt[1] / lt[0] if lt[0] > 0 else pt, lt[3] / lt[2] if lt[2] > 0 else pc)
+                tree.add(lc[1] / lc[0] if lc[0] > 0 else pt, lc[3] / lc[2] if lc[2] > 0 else pc)
+                gains += [0.0, 0.0]
+                f, b, nl = (int(v) for v in best_c[k])
+                tree.feat[node], tree.bin[node], tree.na_left[node], tree.left[node] = f, b, nl, li
+                gains[node] = float(gain_c[k]) * float(tot_c[0, k] + tot_c[2, k])
+                remap[k] = len(parent)
+                parent.append(k)
+                built_right.append(bool(lc[0] + lc[2] < lt[0] + lt[2]))       # build the smaller child
+                new_nodes += [li, li + 1]
+            # route the rows of split nodes to their children and form the build slots' keys
+            br = torch.tensor(built_right, dtype=torch.int32, device=dev)
+            key = uplift_ops.route(codes, nid, cat, rec_d, torch.from_numpy(remap).to(dev), br, nbt)
+            P = len(parent)
+            Hb = self._hist_hip(codes, key, P, nbt, comm)
+            Hpar = Hc[torch.tensor(parent, dtype=torch.long, device=dev)]
+            Hs = Hpar - Hb
+            Hn = torch.empty((2 * P, F, nbt, 4), dtype=torch.int32, device=dev)
             pidx = torch.arange(P, device=dev)
             Hn[2 * pidx + br] = Hb
             Hn[2 * pidx + 1 - br] = Hs
