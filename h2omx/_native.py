@@ -29,7 +29,7 @@ KERNEL_LIBS = {
     "mlp": ["mlp_kernels.hip"],
     "survival": ["cox_kernels.hip"],
     "svm": ["svm_kernels.hip"],
-    "glrm": ["glrm_kernels.hip"],
+    "glrm": ["glrm_kernels.hip", "glrm_loss_kernels.hip"],
     "eif": ["eif_kernels.hip"],
     "uplift": ["uplift_kernels.hip"],
 }

@@ -592,7 +592,16 @@ def _glrm_genmodel(model, info, files):
                 norm_mul=(1.0 / np.where(sc[ncat_cols:] == 0, 1.0, sc[ncat_cols:])).tolist(),
                 transposed=False, reverse_transform=True, seed=int(p.get("seed") or -1),
                 max_iterations=int(p["max_iterations"]))
-    files["losses"] = ("\n".join([str(p["multi_loss"])] * len(cats) + [str(p["loss"])] * len(nums)) + "\n").encode()
+    num_loss = {c: str(p["loss"]) for c in nums}
+    codes = getattr(model, "loss_codes", None)
+    if codes is not None:    # a loss per column and what scoring by proximal gradient needs
+        from ..ops.glrm import LOSSES
+
+        names = {v: n for n, v in LOSSES.items()}
+        num_loss = {c: names[int(codes[j])] for j, (c, lvl) in enumerate(d.spec) if lvl is None}
+        info.update(period=float(p["period"]), init_step_size=float(p["init_step_size"]),
+                    min_step_size=float(p["min_step_size"]))
+    files["losses"] = ("\n".join([str(p["multi_loss"])] * len(cats) + [num_loss[c] for c in nums]) + "\n").encode()
     files["archetypes"] = np.ascontiguousarray(Y, dtype=">f8").tobytes()
 
 
@@ -1009,6 +1018,8 @@ class GenericModel(Model):
                 self.arr[nm] = np.stack([t[j] for t in trees])
         elif a in ("pca", "glrm", "coxph", "extendedisolationforest"):
             self.design = self._design(z, info)
+            if a == "glrm" and "period" in info:    # generalized losses: one name per original column
+                self.glrm_losses = z.read("losses").decode().split()
         names = {"pca": ("center", "scale", "eigenvectors"), "glrm": ("center", "scale", "archetypes"),
                  "isotonicregression": ("thresholds_x", "thresholds_y"), "coxph": ("coef", "x_mean_num"),
                  "extendedisolationforest": ("normals", "offsets", "leaf_sizes"), "gam": ("beta",)}.get(a, ())
@@ -1111,15 +1122,23 @@ class GenericModel(Model):
                 X = (torch.where(torch.isnan(Xraw), m.expand_as(Xraw), Xraw) - c) / s_
                 V = torch.from_numpy(self.arr["eigenvectors"]).to(dev, torch.float32)
                 return V.T @ X
-            from ..models.glrm import _solve_x
+            from ..models.glrm import LossCols, _impute, _solve_x, expanded_codes
 
             A = (Xraw - c) / s_
             mask = ~torch.isnan(A)
             A = torch.where(mask, A, torch.zeros_like(A))
             Y = torch.from_numpy(self.arr["archetypes"]).to(dev, torch.float32)
-            Xk = _solve_x(A.contiguous(), mask, Y, {"regularization_x": info["regularization_x"],
-                                                    "gamma_x": info["gamma_x"]})
-            return (Y.T @ Xk) * s_ + c
+            p_ = {"regularization_x": info["regularization_x"], "gamma_x": info["gamma_x"]}
+            codes = cols = None
+            if getattr(self, "glrm_losses", None):
+                cats, nums = _design_columns(self.design)
+                per = dict(zip(cats + nums, self.glrm_losses))
+                per.update({c_: "Quadratic" for c_ in cats})
+                codes = expanded_codes([per[c_] for c_ in self.design.x], self.design)
+                cols = LossCols(codes, info["period"], dev)
+                p_.update({key: info[key] for key in ("init_step_size", "min_step_size", "max_iterations")})
+            Xk = _solve_x(A.contiguous(), mask, Y, p_, cols)
+            return _impute(Y.T @ Xk, codes) * s_ + c
         if a == "isotonicregression":
             x = frame.vec(self.x[0]).as_float().double()
             tx = torch.from_numpy(self.arr["thresholds_x"]).to(dev)
