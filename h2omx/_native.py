@@ -32,6 +32,7 @@ KERNEL_LIBS = {
     "glrm": ["glrm_kernels.hip", "glrm_loss_kernels.hip"],
     "eif": ["eif_kernels.hip"],
     "uplift": ["uplift_kernels.hip"],
+    "walk": ["walk_kernels.hip"],
 }
 # library name -> extra compiler flags (svm, glrm, eif, uplift: no packed fp32 instructions; uplift also without
 # floating-point contraction, its gains round as the tensor expressions they replace)

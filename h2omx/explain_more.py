@@ -22,7 +22,9 @@
   data behind H2O's explain plots.
 * ``explain(models, frame)``: every applicable piece, as one dict.
 
-All tree walks run as batched device gathers over the ensemble's node table.
+On a device frame the three tree outputs come from the fused ensemble walk of
+``ops.walk`` (``walk_engine`` names the route); CPU frames walk tree by tree as
+batched gathers over the ensemble's node table.
 Every statistic that aggregates rows is all-reduced when a communicator is given.
 """
 from __future__ import annotations
@@ -81,9 +83,8 @@ def _X(model, frame):
     return model._matrix(frame) if hasattr(model, "_matrix") else frame.feature_matrix(model.x)
 
 
-def predict_leaf_node_assignment(model, frame: Frame, type: str = "Path") -> Frame:  # noqa: A002
+def _leaf_torch(model, X: torch.Tensor, type: str = "Path") -> Frame:  # noqa: A002
     ens = _tree_models(model)
-    X = _X(model, frame).float()
     vecs = []
     for t in range(ens.ntrees * ens.K):
         idx, bits, depth, _ = _walk(ens.trees[t], X, _cb(ens, t))
@@ -101,9 +102,8 @@ def predict_leaf_node_assignment(model, frame: Frame, type: str = "Path") -> Fra
     return Frame(vecs)
 
 
-def staged_predict_proba(model, frame: Frame) -> Frame:
+def _staged_torch(model, X: torch.Tensor) -> Frame:
     ens = _tree_models(model)
-    X = _X(model, frame).float()
     K, n = ens.K, X.shape[1]
     acc = torch.zeros((K, n), dtype=torch.float64, device=X.device)
     if not ens.average:
@@ -123,9 +123,8 @@ def staged_predict_proba(model, frame: Frame) -> Frame:
     return Frame(vecs)
 
 
-def feature_frequencies(model, frame: Frame) -> Frame:
+def _frequencies_torch(model, X: torch.Tensor) -> Frame:
     ens = _tree_models(model)
-    X = _X(model, frame).float()
     F, n = X.shape
     cnt = torch.zeros((F + 1, n), dtype=torch.float32, device=X.device)
     for t in range(ens.ntrees * ens.K):
@@ -134,6 +133,92 @@ def feature_frequencies(model, frame: Frame) -> Frame:
             cnt.scatter_add_(0, torch.where(f >= 0, f, torch.full_like(f, F))[None, :],
                              torch.ones((1, n), device=X.device))
     return Frame([Vec(c, cnt[j], "real") for j, c in enumerate(model.x)])
+
+
+def walk_engine(model, X: torch.Tensor, path: bool = False) -> str:
+    """``"hip"`` where the three tree outputs of ``model`` on the matrix ``X [F][n]`` come from
+    ``ops.walk`` (a device matrix of an ensemble ``pack_walk`` accepts), ``"torch"`` where the
+    per-tree tensor walk serves them.  ``path``: the ``Path`` form of the leaf assignment,
+    whose sort key ``depth * 2^40 + bits`` needs every node within depth 40."""
+    from .ops import walk
+
+    ens = getattr(model, "ens", None)
+    if ens is None or not X.is_cuda or ens.ntrees * ens.K < 1:
+        return "torch"
+    try:
+        plan = walk.pack_walk(ens, X.device)
+    except ValueError:
+        return "torch"
+    if plan.max_feat >= X.shape[0] or (path and plan.max_depth > 40):
+        return "torch"
+    return "hip"
+
+
+def _leaf_hip(model, X: torch.Tensor, type: str) -> Frame:  # noqa: A002
+    from .ops import walk
+
+    ens = model.ens
+    plan = walk.pack_walk(ens, X.device)
+    names = [f"T{t // ens.K + 1}.C{t % ens.K + 1}" for t in range(plan.T)]
+    if str(type).lower() == "node_id":
+        ids = walk.leaf_ids(X, plan).float()
+        return Frame([Vec(c, ids[t], "int") for t, c in enumerate(names)])
+    ids, hit = walk.leaf_ids(X, plan, reached=True)
+    hit = hit.cpu().numpy()
+    # a node's path string belongs to the tree alone: the reached nodes of each tree in the order of
+    # depth * 2^40 + bits are its domain, and one table over all trees turns ids into codes
+    table = np.zeros((plan.T, plan.cap), np.int32)
+    doms = []
+    for t in range(plan.T):
+        nid = np.flatnonzero(hit[t])
+        nid = nid[np.argsort(plan.depth[t, nid].astype(np.int64) * (1 << 40) + plan.bits[t, nid], kind="stable")]
+        table[t, nid] = np.arange(len(nid))
+        doms.append(plan.path_strings(t)[nid].tolist())
+    flat = ids + plan.roots[:, None] if plan.T * plan.cap < 1 << 31 else ids.long() + plan.roots.long()[:, None]
+    codes = torch.index_select(torch.from_numpy(table).to(X.device).reshape(-1), 0, flat.reshape(-1)).view_as(ids)
+    return Frame([Vec(c, codes[t], ENUM, doms[t]) for t, c in enumerate(names)])
+
+
+def _staged_hip(model, X: torch.Tensor) -> Frame:
+    from .ops import walk
+
+    ens = model.ens
+    M = walk.staged_margins(X, walk.pack_walk(ens, X.device), ens.init_f, ens.K, ens.average)
+    vecs = []
+    for t in range(ens.ntrees):
+        P = model._link(M[t])
+        if model.category == ModelCategory.BINOMIAL:
+            vecs.append(Vec(f"T{t + 1}.C1", P[-1].float(), "real"))
+        else:
+            for k in range(P.shape[0]):
+                vecs.append(Vec(f"T{t + 1}.C{k + 1}", P[k].float(), "real"))
+    return Frame(vecs)
+
+
+def _frequencies_hip(model, X: torch.Tensor) -> Frame:
+    from .ops import walk
+
+    cnt = walk.feature_counts(X, walk.pack_walk(model.ens, X.device), X.shape[0])
+    return Frame([Vec(c, cnt[j], "real") for j, c in enumerate(model.x)])
+
+
+def predict_leaf_node_assignment(model, frame: Frame, type: str = "Path") -> Frame:  # noqa: A002
+    _tree_models(model)
+    X = _X(model, frame).float()
+    hip = walk_engine(model, X, path=str(type).lower() != "node_id") == "hip"
+    return (_leaf_hip if hip else _leaf_torch)(model, X, type)
+
+
+def staged_predict_proba(model, frame: Frame) -> Frame:
+    _tree_models(model)
+    X = _X(model, frame).float()
+    return (_staged_hip if walk_engine(model, X) == "hip" else _staged_torch)(model, X)
+
+
+def feature_frequencies(model, frame: Frame) -> Frame:
+    _tree_models(model)
+    X = _X(model, frame).float()
+    return (_frequencies_hip if walk_engine(model, X) == "hip" else _frequencies_torch)(model, X)
 
 
 def _glm_design(model, frame: Frame) -> torch.Tensor:
